@@ -7,13 +7,21 @@ encoding) — cut into 8 shards of 32M literals (one hpk_decode_batch launch eac
 ~870 MB encoded). Shard s is decoded by rank s % N, so the same 256M literals are decoded at any
 N ("scaling": "strong"); a step decodes every shard once. The literals are generated on the GPU
 (synth.device_config5_shard, seeded by shard index) and encoded by the library's device encoder;
-every decoded byte of every shard is checked against the generated strings before the warm-up and
-again after the timed steps.
+under --full every decoded byte of every shard is checked against the generated strings before the
+warm-up and again after the timed steps.
+
+A plain run (no --full) sets up, warms up, times the K steps, writes its outputs when --dump-outputs
+DIR is given, and prints the line; its `metric`, `value`, `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` are those of a --full run. Everything else below except `roofline` (which is the
+timed steps' own launch time against committed counter summaries) runs under --full only.
+
+--dump-outputs DIR: what the last timed step decoded (dump_outputs below), the same literals from
+the same inputs in every run, so two builds can be compared array for array.
 
 Timing: barrier + device synchronize on both sides of the K timed steps, HIP events on the stream
 the kernels run on; value = encoded bytes of all shards x K / max over ranks of the time.
 
-Extras on the JSON line:
+Extras on the JSON line (all but roofline need --full):
   roofline      dominant kernel (hpk_decode12): algorithmic bytes per launch (sum over a shard of
                 enc + dec + 13 per literal) / average launch time, against the 8.0 TB/s
                 HBM3E spec peak; traffic = PMC HBM bytes per launch from the committed rocprofv3
@@ -62,7 +70,19 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU of this process's affinity mask, capped at the GPU's host-CPU share (16)")
     ap.add_argument("--pmc-dir", default=os.path.join(REPO, "profiles"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also check every decoded byte before and after timing and run the side measurements "
+                         "(compacted form, configs 2/3/4, host-inclusive, small calls, CPU baselines, and the "
+                         "scatter+decode+gather leg at N > 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step decoded as DIR/<name>.npy (a fixed, "
+                         "seeded sample of literals per shard plus checksums of every decoded byte)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def affinity_cpus():
@@ -493,6 +513,54 @@ def run_config4(codec, threads):
                     "dynamic table"}
 
 
+DUMP_SEED = 7541_64  # the sampled literals are the same in every run and build
+DUMP_SAMPLE = 16384  # literals sampled per launch: 8 shards x 16384 x (64 + 5) values, about 37 MB
+DUMP_WIDTH = 64  # the longest decoded literal of configs 2 and 5
+DUMP_CHUNK = 1 << 22  # literals per checksum
+
+
+def dump_outputs(dirname, entries):
+    """What the timed path's last step returned to its caller, as DIR/<tag>_<name>.npy per launch of
+    the step. entries: (tag, n, out_blob, out_off, out_len, status) device tensors. Per launch:
+      literals  indices of DUMP_SAMPLE literals drawn once from a fixed CPU seed (float64)
+      out_off / out_len / status  of those literals (float64, float32, float32)
+      bytes     their decoded bytes, one row per literal, -1 past out_len (float32)
+      sums      over every literal: per DUMP_CHUNK literals the sum of the decoded bytes, the sum of
+                byte x (1 + position % 65521) over the chunk's bytes end to end, the sum of out_len
+                and the count of non-zero statuses (float64; all exact integers)
+    Only bytes below out_len are read: the slack of a region past it is not part of the result."""
+    import torch
+
+    from loona_amd import synth
+
+    os.makedirs(dirname, exist_ok=True)
+    for k, (tag, n, out, oo, ol, st) in enumerate(entries):
+        g = torch.Generator()
+        g.manual_seed(DUMP_SEED + k)
+        sel = torch.randint(0, n, (min(n, DUMP_SAMPLE),), generator=g).sort().values
+        seld = sel.to(out.device)
+        start = oo[seld].to(torch.int64) & 0xFFFFFFFF
+        ln = ol[seld].to(torch.int64)
+        pos = torch.arange(DUMP_WIDTH, device=out.device)
+        idx = (start[:, None] + pos[None, :]).clamp_(max=out.numel() - 1)
+        rows = torch.where(pos[None, :] < ln[:, None], out[idx].to(torch.float32),
+                           torch.full((), -1.0, device=out.device))
+        sums = []
+        for a in range(0, n, DUMP_CHUNK):
+            b = min(n, a + DUMP_CHUNK)
+            got = synth.gather_output(out, oo, ol, a, b).to(torch.int64)
+            wgt = torch.arange(got.numel(), device=out.device) % 65521 + 1
+            sums.append([int(got.sum().item()), int((got * wgt).sum().item()),
+                         int(ol[a:b].to(torch.int64).sum().item()), int((st[a:b] != 0).sum().item())])
+        for name, arr in (("literals", sel.numpy().astype(np.float64)),
+                          ("out_off", start.cpu().numpy().astype(np.float64)),
+                          ("out_len", ln.cpu().numpy().astype(np.float32)),
+                          ("status", st[seld].cpu().numpy().astype(np.float32)),
+                          ("bytes", rows.cpu().numpy()),
+                          ("sums", np.asarray(sums, dtype=np.float64))):
+            np.save(os.path.join(dirname, f"{tag}_{name}.npy"), arr)
+
+
 def main():
     args = parse()
     import torch
@@ -539,10 +607,11 @@ def main():
         units.append((w, make_unit(codec, w, dev, copies=4)))
         workload = ("config2: 1M short Huffman literals per GPU (decoded len U[8,64], interop-fixture char model, "
                     "canonical RFC 7541 encoding), 4 rotating copies, device-resident")
-    for w, sets in units:
-        for blob, io, out, oo, ol, st in sets:
-            codec.decode_into(blob, io, out, oo, ol, st, device=True, sync=True)
-            synth.check_decoded(w, out, oo, ol, st)  # every byte vs the generated strings
+    if args.full:
+        for w, sets in units:
+            for blob, io, out, oo, ol, st in sets:
+                codec.decode_into(blob, io, out, oo, ol, st, device=True, sync=True)
+                synth.check_decoded(w, out, oo, ol, st)  # every byte vs the generated strings
 
     my_enc = sum(w.enc_bytes for w, _ in units)
     my_dec = sum(w.dec_bytes for w, _ in units)
@@ -586,10 +655,17 @@ def main():
     if world > 1:
         dist.barrier()
     t_ev = ev0.elapsed_time(ev1) / 1e3
-    # the timed launches' results, every byte again (the last launch of each buffer set)
+    # what the last timed step left in the caller's buffers (one buffer set per launch of the step)
+    last = []
     for w, sets in units:
         blob, io, out, oo, ol, st = sets[0] if args.workload == "config5" else sets[(rot[0] - 1) % len(sets)]
-        synth.check_decoded(w, out, oo, ol, st)
+        last.append((w, out, oo, ol, st))
+    if args.dump_outputs:
+        tags = [f"shard{s}" for s in my] if args.workload == "config5" else [f"rank{rank}"]
+        dump_outputs(args.dump_outputs, [(t, w.n, out, oo, ol, st) for t, (w, out, oo, ol, st) in zip(tags, last)])
+    if args.full:  # the timed launches' results, every byte again
+        for w, out, oo, ol, st in last:
+            synth.check_decoded(w, out, oo, ol, st)
     n_launch = args.steps * (len(units) if args.workload == "config5" else 1)
     algo_local = (my_enc + my_dec + 13 * my_n) if args.workload == "config5" else \
         (units[0][0].enc_bytes + units[0][0].dec_bytes + 13 * units[0][0].n)
@@ -605,7 +681,7 @@ def main():
 
     # ---- root-resident form (N > 1): scatter + decode + gather over RCCL, device-resident ----
     e2e = None
-    if world > 1 and args.workload == "config5" and not args.no_e2e:
+    if args.full and world > 1 and args.workload == "config5" and not args.no_e2e:
         from loona_amd.batch import decode_offsets_torch
 
         shards = None
@@ -697,8 +773,11 @@ def main():
             "scaling": "strong" if args.workload == "config5" else "weak",
             "vs_baseline": None,
             "dtype": "u8",
-            "data": "synthetic (generated on the GPU with a seeded torch generator, encoded by the device encoder; "
-                    "every decoded byte checked against the generated strings before and after timing)",
+            "data": "synthetic (generated on the GPU with a seeded torch generator, encoded by the device encoder; " +
+                    ("every decoded byte checked against the generated strings before and after timing)" if args.full
+                     else "the encoder's lengths checked against the code-length sums; the decoded bytes are "
+                          "checked against the generated strings under --full)"),
+            "full": bool(args.full),
             "config": {
                 "workload": workload,
                 "literals_total": int(all_n),
@@ -735,10 +814,10 @@ def main():
             line["e2e_scatter_decode_gather"] = e2e
 
     # ---- the compacted form, config-2 side measurement and CPU baselines (rank 0) ----
-    if rank == 0 and args.workload == "config5" and not args.no_compact:
+    if args.full and rank == 0 and args.workload == "config5" and not args.no_compact:
         line["config5_compact"] = run_compact(codec, units[0][0], stream, args.pmc_dir)
         torch.cuda.empty_cache()
-    if rank == 0 and args.workload == "config5" and not args.no_config2:
+    if args.full and rank == 0 and args.workload == "config5" and not args.no_config2:
         del units, by_shard
         torch.cuda.empty_cache()
         w2 = synth.device_config2(codec, 1_000_000, seed=synth.SEED, device=dev)
@@ -760,12 +839,12 @@ def main():
         cpu_w = w2
     elif rank == 0:
         cpu_w = units[0][0]
-    if rank == 0 and args.workload == "config5" and not args.no_config3:
+    if args.full and rank == 0 and args.workload == "config5" and not args.no_config3:
         line["config3"] = run_config3(codec, stream, dev)
         torch.cuda.empty_cache()
-    if rank == 0 and args.workload == "config5" and not args.no_config4:
+    if args.full and rank == 0 and args.workload == "config5" and not args.no_config4:
         line["config4"] = run_config4(codec, cpu_threads(args.cpu_threads)[0])
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         blob_h = cpu_w.enc_blob.cpu().numpy()
         off_h = cpu_w.enc_off.cpu().numpy().view(np.uint32).copy()
         th, aff = cpu_threads(args.cpu_threads)

@@ -258,6 +258,15 @@ def last_error() -> str:
     return msg.decode(errors="replace") if msg else ""
 
 
+def clear_hip_error() -> None:
+    """Read, and so reset, the calling thread's last HIP error (hipGetLastError, reached through
+    libhpk.so's own link to the HIP runtime)."""
+    fn = lib().hipGetLastError
+    fn.argtypes = []
+    fn.restype = ctypes.c_int
+    fn()
+
+
 def check(rc: int, what: str) -> int:
     if rc < 0:
         raise RuntimeError(f"{what} failed ({rc}): {last_error()}")

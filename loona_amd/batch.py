@@ -135,6 +135,10 @@ class HuffmanCodec:
         if getattr(self, "_h", None):
             self._L.hpk_ctx_destroy(self._h)
             self._h = None
+            # hpk_ctx_destroy ignores what its HIP calls return (waiting for a slot's event whose stream
+            # the caller has destroyed since can fail), but HIP keeps a thread's last failure, and torch
+            # reads it after its next kernel launch and raises it as that launch's. Take it away here.
+            _lib.clear_hip_error()
 
     def __del__(self):
         try:
