@@ -15,7 +15,7 @@
 
 #include <vector>
 
-#include "../loona_amd/csrc/hpk_wave.h"
+#include "../loona_amd/csrc/hpk_walk.h"
 
 #define CK(x)                                                                                 \
     do {                                                                                      \

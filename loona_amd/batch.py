@@ -287,7 +287,7 @@ class HuffmanCodec:
         literal i is out_blob[out_off[i] : out_off[i] + out_len[i]] and out_off[n] is the end of the span
         written to. out_off is an output (n + 1 entries; runs of literals in completion order, so not
         monotone). The span is not gap-free: listed (long / huge) literals keep their decoded bound, and
-        the wave-fill kernel (>= 4M literals) packs per workgroup, each share ending in an unwritten tail
+        the wave-fill kernel (every auto or wave batch) packs per workgroup, each share ending in an unwritten tail
         (include/hpk.h); shard.compact gathers the bytes end to end."""
         import torch
 

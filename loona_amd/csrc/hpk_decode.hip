@@ -6,14 +6,15 @@
 // and status Ok / PaddingTooLarge / InvalidPadding / EOSInString with the reference's precedence.
 //
 // Two kernels, identical results (tests/test_gpu.py runs every case through both):
-//   * hpk_decode_wave (v25, hpk_wave.h), for large batches: every wave of a 1024-thread workgroup
+//   * hpk_decode_wave (v25, hpk_wave.h), for every batch: every wave of a 1024-thread workgroup
 //     decodes its own fills of <= 128 literals (two per lane, longest with shortest) out of its own
 //     LDS window into its own LDS image, with no barrier between fills, so the waves' memory traffic
 //     and setup overlap each other's decoding; the workgroup's range is handed out in chunks;
-//   * hpk_decode12 (v24, hpk_decode12.h), for small batches: one workgroup-wide fill at a time per
-//     CU (40 KiB window, 77 KiB image, 2048-literal longest-first queue), the next fill's loads in
-//     flight during the decode, the previous image written back around it.
-// Both use the same lane walk (hpk_decode12.h): a step is two lookups in the 12-bit two-symbol
+//   * hpk_decode12 (v24, hpk_fill.h), only when forced (hpk_ctx_set_decode_kernel(HPK_DECODE_FILL)):
+//     one workgroup-wide fill at a time per CU (40 KiB window, 77 KiB image, 2048-literal
+//     longest-first queue), the next fill's loads in flight during the decode, the previous image
+//     written back around it.
+// Both use the same lane walk (hpk_walk.h): a step is two lookups in the 12-bit two-symbol
 // table, each decoding up to two codes of <= 12 bits, from a 32-bit window made by ONE v_alignbit
 // out of a register-held dword pair; a longer code (or EOS) takes one leading-ones lookup. Bits past
 // a literal's end are not masked: a code that runs past the end is, by prefix-freeness, longer than
@@ -26,13 +27,13 @@
 
 #include <chrono>
 
-
+#include "hpk_fill.h"
 #include "hpk_wave.h"
 #include "hpk_persist.h"
 
 using namespace hpkdec;
 
-// Workgroup-fill kernel (v24, hpk_decode12.h): 16 waves (one 1024-thread workgroup) per CU; per
+// Workgroup-fill kernel (v24, hpk_fill.h): 16 waves (one 1024-thread workgroup) per CU; per
 // fill a 40 KiB input window, a 77 KiB output image and a 2048-entry longest-first queue, plus the
 // 16 KiB two-symbol table; lanes check for a finished literal every 2 steps.
 constexpr int kWaves = 16, kW = 40960, kO = 79104, kQ = 2048, kRefillN = 2;
@@ -46,12 +47,13 @@ constexpr int kWaves = 16, kW = 40960, kO = 79104, kQ = 2048, kRefillN = 2;
 #endif
 using Geo = Geo12<kWaves, kW, kO, kQ>;
 // Wave-fill kernel (v25, hpk_wave.h): per wave a 3 KiB window and a 5.75 KiB image, the workgroup's
-// range handed out in chunks of 224 literals; for batches of at least HPK_WAVE_MIN literals (smaller
-// ones keep the workgroup-fill kernel) unless the context says otherwise (hpk_ctx_set_decode_kernel)
+// range handed out in chunks of 224 literals; it runs every batch (HPK_WAVE_MIN is 0) unless the context
+// forces the workgroup-fill kernel (hpk_ctx_set_decode_kernel)
 constexpr int kWaveWin = 3072, kWaveImg = 5888;
 #ifndef HPK_WAVE_MIN
-#define HPK_WAVE_MIN 0u  // (round 6: the wave kernel for every batch; it had been 4M: config 2 40.3-40.8 vs 47.1-47.3 us
-                         // for the workgroup-fill kernel, 1k-literal synchronous calls 21.5 vs 24.4 us)
+#define HPK_WAVE_MIN 0u  // least literals of a batch the wave kernel takes in HPK_DECODE_AUTO: every batch since round 6
+                         // (it had been 4M: config 2 40.3-40.8 vs 47.1-47.3 us for the workgroup-fill kernel,
+                         // 1k-literal synchronous calls 21.5 vs 24.4 us)
 #endif
 #ifndef HPK_WAVE_GUIDED
 #define HPK_WAVE_GUIDED 1  // chunks claimed by the waves (1: guided self-scheduling, 2: fixed HPK_WAVE_CHUNK) vs a static 1/16 each (0)
@@ -78,10 +80,24 @@ constexpr int kWaveWin = 3072, kWaveImg = 5888;
 #ifdef HPK_DIAG
 // Diagnostic build (libhpk_diag.so, `make diag`; never the product library): HPK_DEBUG_MODE selects
 // 1 no decode, 2 no output stores, 3 per-wave stamps (16 x u64 per wave, hpk_debug_stamps),
-// 4 every store bounds-checked (hpk_debug_check).
+// 4 every store bounds-checked (fill kernel, hpk_debug_check), 5 per-wave counters of the long-literal
+// phase, 6 VALU sensitivity, 8-10 LDS conflict attribution (wave kernel, lit12_body's kDup: the table
+// reads / the window read / the byte stores issued twice).
 static int g_debug_mode = -1;
 static unsigned long long* g_dbg = nullptr;
 static size_t g_dbg_n = 0;
+
+// a.dbg for a launch that writes `need` u64 entries (grow-only), zeroed on the stream if asked
+static int dbg_buffer(hpk_ctx* c, DecodeArgs& a, size_t need, bool zero) {
+    if (need > g_dbg_n) {
+        (void)hipFree(g_dbg);
+        HIP_TRY(hipMalloc(&g_dbg, need * 8));
+        g_dbg_n = need;
+    }
+    if (zero) HIP_TRY(hipMemsetAsync(g_dbg, 0, need * 8, c->stream));
+    a.dbg = g_dbg;
+    return HPK_E_OK;
+}
 
 extern "C" int hpk_debug_check(unsigned long long* host8) {
     return hipMemcpyFromSymbol(host8, HIP_SYMBOL(g_chk), 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
@@ -306,11 +322,11 @@ int hpk_persist_start(hpk_ctx* c) { return persist_launch(c, c->sm_req); }
 
 extern "C" uint64_t hpk_test_small_calls(const hpk_ctx* c) { return c ? c->sm_calls : 0u; }
 
-extern "C" int hpk_test_small_stamps(const hpk_ctx* c, uint32_t* out6) {  // (10 values)
-    if (!c || !c->h_sm || !out6) return HPK_E_INVAL;
+extern "C" int hpk_test_small_stamps(const hpk_ctx* c, uint32_t* out10) {
+    if (!c || !c->h_sm || !out10) return HPK_E_INVAL;
     const auto* h = static_cast<const PersistCtl*>(c->h_sm);
-    for (int k = 0; k < 6; ++k) out6[k] = __atomic_load_n(&h->ts[k], __ATOMIC_ACQUIRE);
-    for (int k = 0; k < 4; ++k) out6[6 + k] = __atomic_load_n(&h->tl[k], __ATOMIC_ACQUIRE);
+    for (int k = 0; k < 6; ++k) out10[k] = __atomic_load_n(&h->ts[k], __ATOMIC_ACQUIRE);
+    for (int k = 0; k < 4; ++k) out10[6 + k] = __atomic_load_n(&h->tl[k], __ATOMIC_ACQUIRE);
     return HPK_E_OK;
 }
 
@@ -429,93 +445,31 @@ int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b) {
         HIP_TRY(hipGetLastError());
         return hpk_long_list_used(c, lslot);
     }
-    if (wave) {
-        // (every mode runs the kernel the product would: fixed chunks below HPK_WAVE_GUIDED_MIN literals)
-#define WAVE_LAUNCH(m)                                                                    \
-    do {                                                                                  \
-        if (b.n < HPK_WAVE_GUIDED_MIN)                                                    \
-            hipLaunchKernelGGL(WAVE_KERNEL_SMALL(m), grid, block, 0, c->stream, a);       \
-        else                                                                              \
-            hipLaunchKernelGGL(WAVE_KERNEL(m), grid, block, 0, c->stream, a);             \
-    } while (0)
-        if (g_debug_mode == 1) {
-            WAVE_LAUNCH(1);
-        } else if (g_debug_mode == 3) {
-            const size_t need = (size_t)blocks * kWaves * 16;
-            if (need > g_dbg_n) {
-                (void)hipFree(g_dbg);
-                HIP_TRY(hipMalloc(&g_dbg, need * 8));
-                g_dbg_n = need;
-            }
-            a.dbg = g_dbg;
-            WAVE_LAUNCH(3);
-        } else if (g_debug_mode == 2)
-            WAVE_LAUNCH(2);
-        else if (g_debug_mode == 6)
-            WAVE_LAUNCH(6);
-        else if (g_debug_mode == 7)
-            WAVE_LAUNCH(7);
-        else if (g_debug_mode == 8)  // LDS conflict attribution (lit12_body's kDup): table reads twice
-            WAVE_LAUNCH(8);
-        else if (g_debug_mode == 9)  // the window read twice
-            WAVE_LAUNCH(9);
-        else if (g_debug_mode == 10)  // the byte stores twice
-            WAVE_LAUNCH(10);
-        else if (g_debug_mode == 5) {  // per-wave counters of the long-literal phase (HPK_LONG_WAVES waves)
-            const size_t need = (size_t)blocks * HPK_LONG_WAVES * 16;
-            if (need > g_dbg_n) {
-                (void)hipFree(g_dbg);
-                HIP_TRY(hipMalloc(&g_dbg, need * 8));
-                g_dbg_n = need;
-            }
-            HIP_TRY(hipMemsetAsync(g_dbg, 0, need * 8, c->stream));
-            a.dbg = g_dbg;
-            if (b.n < HPK_WAVE_GUIDED_MIN)
-                hipLaunchKernelGGL(WAVE_KERNEL_SMALL(5), grid, block, 0, c->stream, a);
-            else
-                WAVE_LAUNCH(5);
-        } else if (b.n < HPK_WAVE_GUIDED_MIN)  // (the product's choice)
-            hipLaunchKernelGGL(WAVE_KERNEL_SMALL(0), grid, block, 0, c->stream, a);
-        else
-            WAVE_LAUNCH(0);
-        HIP_TRY(hipGetLastError());
-        return hpk_long_list_used(c, lslot);
+    // modes 3 and 5 write per-wave entries (16 each) into a.dbg; mode 5 adds to them, so they start zeroed
+    if (g_debug_mode == 3 || g_debug_mode == 5) {
+        const size_t waves = g_debug_mode == 3 ? kWaves : HPK_LONG_WAVES;
+        if (int rc = dbg_buffer(c, a, (size_t)blocks * waves * 16, g_debug_mode == 5)) return rc;
     }
-    switch (g_debug_mode) {
-        case 1:
-            hipLaunchKernelGGL(DEC_KERNEL(1), grid, block, 0, c->stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL(DEC_KERNEL(2), grid, block, 0, c->stream, a);
-            break;
-        case 3: {
-            const size_t need = (size_t)blocks * kWaves * 16;
-            if (need > g_dbg_n) {
-                (void)hipFree(g_dbg);
-                HIP_TRY(hipMalloc(&g_dbg, need * 8));
-                g_dbg_n = need;
-            }
-            a.dbg = g_dbg;
-            hipLaunchKernelGGL(DEC_KERNEL(3), grid, block, 0, c->stream, a);
-            break;
+    // (every mode runs the kernel the product would: fixed chunks below HPK_WAVE_GUIDED_MIN literals)
+#define WAVE_MODE(m)                                                                  \
+    case m:                                                                           \
+        if (b.n < HPK_WAVE_GUIDED_MIN)                                                \
+            hipLaunchKernelGGL(WAVE_KERNEL_SMALL(m), grid, block, 0, c->stream, a);   \
+        else                                                                          \
+            hipLaunchKernelGGL(WAVE_KERNEL(m), grid, block, 0, c->stream, a);         \
+        break;
+#define FILL_MODE(m) \
+    case m: hipLaunchKernelGGL(DEC_KERNEL(m), grid, block, 0, c->stream, a); break;
+    if (wave) {
+        switch (g_debug_mode) {
+            WAVE_MODE(1) WAVE_MODE(2) WAVE_MODE(3) WAVE_MODE(5) WAVE_MODE(6) WAVE_MODE(8) WAVE_MODE(9) WAVE_MODE(10)
+            default: WAVE_MODE(0)
         }
-        case 4:
-            hipLaunchKernelGGL(DEC_KERNEL(4), grid, block, 0, c->stream, a);
-            break;
-        case 5: {  // the product kernel with per-wave counters of the long-literal phase (8 waves)
-            const size_t need = (size_t)blocks * 8 * 16;
-            if (need > g_dbg_n) {
-                (void)hipFree(g_dbg);
-                HIP_TRY(hipMalloc(&g_dbg, need * 8));
-                g_dbg_n = need;
-            }
-            HIP_TRY(hipMemsetAsync(g_dbg, 0, need * 8, c->stream));
-            a.dbg = g_dbg;
-            hipLaunchKernelGGL(DEC_KERNEL(5), grid, block, 0, c->stream, a);
-            break;
+    } else {
+        switch (g_debug_mode) {
+            FILL_MODE(1) FILL_MODE(2) FILL_MODE(3) FILL_MODE(4) FILL_MODE(5)
+            default: FILL_MODE(0)
         }
-        default:
-            hipLaunchKernelGGL(DEC_KERNEL(0), grid, block, 0, c->stream, a);
     }
 #else
     if (wave && b.n < HPK_WAVE_GUIDED_MIN)

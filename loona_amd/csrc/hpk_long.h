@@ -41,7 +41,6 @@
 // Semantics are the fill kernel's lane walk (huffman.rs:95-161): the walk stops where no code fits,
 // an EOS is EOSInString at once, then >7 residual bits PaddingTooLarge, non-ones InvalidPadding.
 #pragma once
-// (included by hpk_decode12.h after the lane-walk helpers it uses: lut12, residual_status, lo_decode)
 #include "hpk_decode_kernel.h"
 
 namespace hpkdec {

@@ -3,7 +3,7 @@
 // doorbell, so a small call skips the kernel launch (~4 us of API, ~5 us to the kernel's start) and
 // the stream synchronisation (~5 us from the kernel's end to the host's wake-up) of the launch path
 // (DESIGN.md §6). One lane per literal, walking its input straight from global memory with the
-// two-symbol table (the huge phase's walker, hpk_huge.h) and storing whole 8-byte groups.
+// two-symbol table (the huge phase's walker, hpk_huge_piece.h) and storing whole 8-byte groups.
 //
 // Protocol (PersistCtl lives in host memory, coherent and mapped; the host writes a request's
 // fields, then req; the device answers with done = req):
@@ -21,6 +21,8 @@
 //     workgroup 0 always broadcasts first). Nothing loops on a value only the host could change
 //     without a deadline.
 #pragma once
+#include "hpk_decode_kernel.h"
+#include "hpk_huge_piece.h"
 
 namespace hpkdec {
 
@@ -82,7 +84,7 @@ __device__ __forceinline__ void st_sys(uint32_t* p, uint32_t v) {
 // One literal: huffman.rs:95-161 semantics (a code that runs past the end ends the walk, EOS is
 // EOSInString at once, then > 7 residual bits PaddingTooLarge, non-ones InvalidPadding), and the batch
 // ABI's capacity check per byte (HPK_OUTPUT_OVERFLOW, as the fill kernels' byte path:
-// hpk_decode_kernel.h lit_bytes_to). Returns false (nothing written) if the literal's offsets are bad.
+// hpk_walk.h lit_bytes_to). Returns false (nothing written) if the literal's offsets are bad.
 template <class Ld>
 __device__ bool persist_literal(const Ld& ld16, const uint32_t* __restrict__ lut, const uint16_t* __restrict__ lo,
                                 HPK_GAS uint8_t* out_base, uint32_t out_mis, uint32_t in_mis, uint32_t p0, uint32_t p1,

@@ -1,0 +1,430 @@
+// hpk_walk.h — everything a single lane needs to decode a literal: the lane walk every decode kernel
+// uses (hpk_wave.h, hpk_fill.h, hpk_long.h) and the code-by-code byte path. Plain per-lane code: the
+// including file provides the HIP runtime, or tests/emu/shim.h (which stands in for the handful of
+// builtins used here) when tests/emu replays these functions on the CPU against the oracle.
+//   * Lane walk (v12): a lane holds its bit position as X = P + 31 and the dword pair (d0, d1) =
+//     window dwords (X >> 5) - 1 and X >> 5, plus the next dword d2. The 32 bits at P are ONE
+//     v_alignbit_b32(d0, d1, ~X). A step does two lookups in the two-symbol table (LUT2 / LUT3 layout,
+//     hpk_code.h), each decoding up to two codes of <= 12 bits, and advances <= 24 bits, so it crosses
+//     at most one dword: the pair then slides by one (v_cndmask) and d2 takes d3, the dword read at the
+//     top of the step. A code longer than 12 bits (EOS included) takes the rarely taken branch: one
+//     leading-ones lookup. Bits past a literal's end are never masked: a code that runs past the end is,
+//     by prefix-freeness, longer than what is left whatever follows, so the walk stops exactly where
+//     huffman.rs's bit iterator stops matching (huffman.rs:100-123); the final padding check
+//     (huffman.rs:128-160) looks at the residual bits only.
+//   * Stores (v14): a checked step's (up to) four byte stores are unconditional, a byte that is not
+//     output going to the lane's dummy slot (no exec-mask branch around each ds_write_b8).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/hpk.h"
+#include "hpk_code.h"
+
+namespace hpkdec {
+
+enum StoreMode { kDword = 0, kNoStore = 1, kChecked = 3, kPred = 4 };  // kPred: kDword, lane steps store
+// unconditionally, a byte that is not output going to a per-lane dummy slot
+
+// diagnostic mode 4 (kChecked): record the first out-of-region store instead of performing it
+#ifdef __HIPCC__
+__device__ unsigned long long g_chk[8];
+__device__ __forceinline__ void chk_report(uint32_t code, uint32_t a0, uint32_t a1, uint32_t a2) {
+    if (atomicCAS(&g_chk[0], 0ull, (unsigned long long)code) == 0ull) {
+        g_chk[1] = a0;
+        g_chk[2] = a1;
+        g_chk[3] = a2;
+        g_chk[4] = blockIdx.x;
+        g_chk[5] = threadIdx.x;
+    }
+}
+#else
+inline void chk_report(uint32_t, uint32_t, uint32_t, uint32_t) {}
+#endif
+
+__device__ __forceinline__ void put8(uint8_t* __restrict__ out8, uint32_t pos, uint32_t v, uint32_t oend, int kStore) {
+    if (kStore == kChecked) {
+        if (pos < oend)
+            out8[pos] = (uint8_t)v;
+        else
+            chk_report(1, pos, oend, 0);
+    } else if (kStore == kDword || kStore == kPred) {
+        out8[pos] = (uint8_t)v;
+    } else {
+        asm volatile("" ::"v"(v));
+    }
+}
+
+// The 32 window bits at bit position p (big-endian dwords).
+__device__ __forceinline__ uint32_t win_at(const uint32_t* __restrict__ win32, uint32_t p) {
+    const uint32_t x = p + 31u;
+    const uint32_t* q = win32 + (x >> 5);
+    return __builtin_amdgcn_alignbit(q[-1], q[0], ~x);
+}
+
+// The codes one table entry decodes with rem bits left: ok1 / ok2 = its first / second code fits
+// inside the literal; returns the bits they use.
+template <int kTab = 2>  // the table layout: 2 = LUT2, 3 = LUT3 (hpk_code.h)
+__device__ __forceinline__ uint32_t lut12(uint32_t e, uint32_t rem, bool& ok1, bool& ok2) {
+    // a length field the entry does not hold is 15, past any clamped rem (and t1 >= l1: ok2 => ok1)
+    const uint32_t rc = min(rem, HPK_LUT2_CLAMP);
+    if (kTab == 3) {
+        const uint32_t l1 = HPK_L3_LEN0(e), t1 = HPK_L3_HELD(e);
+        ok1 = l1 <= rc;
+        ok2 = (t1 <= rc) & (e < HPK_L3_NOTTWO);
+        return ok2 ? t1 : (ok1 ? l1 : 0u);
+    }
+    const uint32_t l1 = HPK_L2_LEN0(e), t1 = HPK_L2_LEN01(e);
+    ok1 = l1 <= rc;
+    ok2 = t1 <= rc;
+    return ok2 ? t1 : (ok1 ? l1 : 0u);
+}
+template <int kTab>
+__device__ __forceinline__ bool lut_nottwo(uint32_t e) {
+    return kTab == 3 ? e >= HPK_L3_NOTTWO : e >= HPK_LUT2_NOTTWO;
+}
+// An entry's second symbol byte, in place for a byte store (LUT2 / LUT3: [23:16])
+template <int kTab>
+__device__ __forceinline__ uint32_t lut_sym1(uint32_t e) {
+    return e >> 16;
+}
+
+// Final status at a stop with rem residual bits and window w there (huffman.rs:128-160): at most
+// 7 residual bits, all ones (the most significant bits of EOS).
+__device__ __forceinline__ uint32_t residual_status(uint32_t rem, uint32_t w) {
+    if (rem == 0) return HPK_OK;
+    if (rem > 7) return HPK_PADDING_TOO_LARGE;
+    return (w | (0xFFFFFFFFu >> rem)) != 0xFFFFFFFFu ? HPK_INVALID_PADDING : HPK_OK;
+}
+
+// Decode one code of any length from the window (>= 30 loaded bits): leading-ones table.
+__device__ __forceinline__ void lo_decode(uint32_t w, const uint16_t* __restrict__ lo, uint32_t& sym,
+                                          uint32_t& len, bool& eos) {
+    const uint32_t kk = __clz(~w);
+    const uint32_t e = lo[min(kk, (uint32_t)HPK_LO_RUNS - 1) * 32 + ((w << ((kk + 1) & 31)) >> 27)];
+    eos = kk >= HPK_LO_RUNS || (e & 0x1FFu) == HPK_EOS;
+    sym = e & 0xFFu;
+    len = eos ? 30u : (e >> 9);
+}
+
+// ------------------------------------------------------------------------------------------
+// Lane-per-literal walk.
+
+struct Lit12 {
+    uint32_t X;           // bit position in the window + 31
+    uint32_t Eb;          // end bit position + 31: rem = Eb - X bits left
+    uint32_t d0, d1, d2;  // window dwords (X >> 5) - 1, X >> 5, (X >> 5) + 1
+    uint32_t o;           // next output byte in the LDS image
+    uint32_t o0;          // first output byte of the literal
+    uint32_t oend;        // checked mode: end of the literal's capacity
+    uint32_t st;          // hpk_status set by the walk (EOS, or padding found by the long-code branch)
+    uint32_t idx;         // literal index in the fill
+    bool prog;            // the last step consumed a code or took the long-code branch
+    bool more;            // (kMore steps) the walk may go on: the last step used both entries whole, or
+                          // decoded a long code; false once a step has proved that no code fits
+    bool act;             // holds a fast-path literal not yet finalised
+};
+
+// (Re)load the pair and the next dword at X.
+__device__ __forceinline__ void lit12_load(Lit12& L, const uint32_t* __restrict__ win32) {
+    const uint32_t* p = win32 + (L.X >> 5);
+    L.d0 = p[-1];
+    L.d1 = p[0];
+    L.d2 = p[1];
+}
+
+// lit12_step's first part: the two lookups and their stores; returns whether a 13..30-bit code or EOS
+// starts at the new position (lit12_park then does its leading-ones lookup).
+template <int kStore, bool kP1, int kTab, bool kMore>
+__device__ __forceinline__ bool lit12_step_main(Lit12& L, const uint32_t* __restrict__ win32,
+                                                const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8,
+                                                uint32_t dmy) {
+    const uint32_t d3 = win32[(L.X >> 5) + 2];  // the dword after d2, in case this step crosses one
+    const uint32_t w = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
+    const uint32_t rem = L.Eb - L.X;
+    const uint32_t e1 = lut[w >> (32 - HPK_LUT_BITS)];
+    bool a1, a2;
+    const uint32_t u1 = lut12<kTab>(e1, rem, a1, a2);
+    uint32_t use = u1;
+    // a code longer than 12 bits (or EOS) starts here and may still fit (with more than 12 bits
+    // left, any code the entry holds fits: no first code <=> the entry has none)
+    bool park = !a1 & (rem > (uint32_t)HPK_LUT_BITS);
+    bool more2 = false;
+    if (kStore == kPred) {
+        out8[a1 ? L.o : dmy] = (uint8_t)e1;
+        if (kP1)
+            (out8 + 1)[a2 ? L.o : dmy - 1u] = (uint8_t)lut_sym1<kTab>(e1);
+        else
+            out8[a2 ? L.o + 1 : dmy] = (uint8_t)lut_sym1<kTab>(e1);
+    } else {
+        if (a1) put8(out8, L.o, e1, L.oend, kStore);
+        if (a2) put8(out8, L.o + 1, lut_sym1<kTab>(e1), L.oend, kStore);
+    }
+    L.o += (uint32_t)a1 + (uint32_t)a2;
+    {
+        // the first entry was consumed whole: look the next bits up too
+        const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
+        const uint32_t w2 = w << u1;
+        const uint32_t rem2 = rem - u1;
+        const uint32_t e2 = lut[w2 >> (32 - HPK_LUT_BITS)];
+        bool b1, b2;
+        const uint32_t u2 = lut12<kTab>(e2, rem2, b1, b2);
+        park |= cont & !b1 & (rem2 > (uint32_t)HPK_LUT_BITS);
+        b1 &= cont;
+        b2 &= cont;
+        // both entries used whole: more codes may follow (otherwise one of them held a code that does
+        // not fit, or none with <= 12 bits left: the walk has ended here, huffman.rs:100-123)
+        more2 = b1 & (b2 | lut_nottwo<kTab>(e2));
+        if (kStore == kPred) {
+            out8[b1 ? L.o : dmy] = (uint8_t)e2;
+            if (kP1)
+                (out8 + 1)[b2 ? L.o : dmy - 1u] = (uint8_t)lut_sym1<kTab>(e2);
+            else
+                out8[b2 ? L.o + 1 : dmy] = (uint8_t)lut_sym1<kTab>(e2);
+        } else {
+            if (b1) put8(out8, L.o, e2, L.oend, kStore);
+            if (b2) put8(out8, L.o + 1, lut_sym1<kTab>(e2), L.oend, kStore);
+        }
+        L.o += (uint32_t)b1 + (uint32_t)b2;
+        use += cont ? u2 : 0u;
+    }
+    const uint32_t xn = L.X + use;
+    const bool cross = (xn ^ L.X) > 31u;
+    L.d0 = cross ? L.d1 : L.d0;
+    L.d1 = cross ? L.d2 : L.d1;
+    L.d2 = cross ? d3 : L.d2;
+    L.X = xn;
+    L.prog = a1 | park;
+    if (kMore) L.more = park | more2;
+    return park;
+}
+
+template <int kStore, bool kMore>
+__device__ __forceinline__ void lit12_park(Lit12& L, const uint32_t* __restrict__ win32, const uint16_t* __restrict__ lo,
+                                           uint8_t* __restrict__ out8) {
+    // a 13..30-bit code or EOS: one leading-ones lookup (any code in one read)
+    const uint32_t wp = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
+    uint32_t s, len;
+    bool eos;
+    lo_decode(wp, lo, s, len, eos);
+    const uint32_t r = L.Eb - L.X;
+    if (len > r) {  // nothing fits in the > 12 bits left: huffman.rs:128-134
+        L.st = HPK_PADDING_TOO_LARGE;
+        L.Eb = L.X;
+        if (kMore) L.more = false;
+    } else if (eos) {  // huffman.rs:112-116
+        L.st = HPK_EOS_IN_STRING;
+        L.Eb = L.X;
+        if (kMore) L.more = false;
+    } else {
+        put8(out8, L.o, s, L.oend, kStore);
+        L.o += 1;
+        L.X += len;
+        lit12_load(L, win32);
+    }
+}
+
+// One step: two lookups (up to four codes of <= 12 bits) and, for a longer code, one leading-ones
+// lookup. kStore == kPred: the (up to) four byte stores are unconditional, a byte that is not output
+// going to the lane's dummy slot out8[dmy] (no exec-mask branch around each store); kChecked
+// (diagnostic mode 4) checks every store against the literal's capacity, kNoStore (mode 2) stores
+// nothing.
+template <int kStore, bool kP1 = false,   // kP1: a lookup's second byte stored at (address) + 1 by the
+          int kTab = 2,                  // store's offset (the wave kernel; in the fill kernel's
+          bool kMore = false>            // register budget the extra live dmy - 1 spills); kTab: lut12;
+                                         // kMore: set L.more (the tails of decode v27)
+__device__ __forceinline__ void lit12_step(Lit12& L, const uint32_t* __restrict__ win32, const uint32_t* __restrict__ lut,
+                                           const uint16_t* __restrict__ lo, uint8_t* __restrict__ out8,
+                                           uint32_t dmy = 0) {
+    if (lit12_step_main<kStore, kP1, kTab, kMore>(L, win32, lut, out8, dmy)) lit12_park<kStore, kMore>(L, win32, lo, out8);
+}
+
+// Body step (decode v27): the same two lookups with NO fit tests, for a literal with at least
+// kBodyMin bits left before the step. A step consumes <= 24 bits, so every code the two entries hold
+// ends inside the literal, and >= 13 bits are left after it. The stores are unconditional at the
+// lane's own output positions: an entry's second byte when it holds one code (or both bytes when it
+// holds none) is garbage that the next store overwrites, or lies past the decoded bytes inside the
+// literal's own region (see kBodyMin). Lengths come from the entries' "bits held" and "codes held" fields: ~25 VALU per
+// step against lit12_step's ~48. A lookup that holds no code (a 13..30-bit code or EOS) takes the
+// checked leading-ones branch of lit12_step; `body` says whether the next step may be a body step.
+#ifndef HPK_BODY_MIN
+#define HPK_BODY_MIN 29
+#endif
+// 24 bits a step may consume + 5: after a body step >= 5 bits are left, so when the decoded bytes end
+// there the decoded length is below the bound (a code is >= 5 bits) and a garbage byte at the next
+// output position stays in the region; a lookup holding no code has >= 29 - 12 > 12 bits left, so it
+// always takes the leading-ones branch (whose symbol overwrites the garbage)
+constexpr uint32_t kBodyMin = HPK_BODY_MIN;
+
+// kDup (diagnostic builds, LDS bank-conflict attribution): one access class of the step issued twice,
+// the extra access a volatile one through an LDS-qualified pointer (a volatile access through a generic
+// pointer became a flat access, and a later plain store to the same byte let the compiler drop the
+// earlier one): 1 the two table reads, 2 the window read, 3 the four byte stores (the same bytes, the
+// duplicate first). The conflict cycles a variant adds over the product are that class's.
+#ifndef HPK_LDS_AS
+#define HPK_LDS_AS __attribute__((address_space(3)))
+#endif
+template <int kStore, int kTab = 2, int kDup = 0>
+__device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict__ win32, const uint32_t* __restrict__ lut,
+                                           const uint16_t* __restrict__ lo, uint8_t* __restrict__ out8, bool& body) {
+    const uint32_t d3 = win32[(L.X >> 5) + 2];
+    if (kDup == 2) asm volatile("" ::"v"(((const volatile HPK_LDS_AS uint32_t*)win32)[(L.X >> 5) + 2]));
+    const uint32_t w = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
+    const uint32_t e1 = lut[w >> (32 - HPK_LUT_BITS)];
+    const uint32_t u1 = kTab == 3 ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
+    const uint32_t e2 = lut[(w << u1) >> (32 - HPK_LUT_BITS)];
+    if (kDup == 1) {
+        const volatile HPK_LDS_AS uint32_t* vl = (const volatile HPK_LDS_AS uint32_t*)lut;
+        asm volatile("" ::"v"(vl[w >> (32 - HPK_LUT_BITS)]));
+        asm volatile("" ::"v"(vl[(w << u1) >> (32 - HPK_LUT_BITS)]));
+    }
+    const uint32_t u2 = kTab == 3 ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
+    const uint32_t o1 = L.o + (kTab == 3 ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1));
+    if (kStore != kNoStore) {
+        if (kDup == 3) {
+            volatile HPK_LDS_AS uint8_t* v8 = (volatile HPK_LDS_AS uint8_t*)out8;
+            v8[L.o] = (uint8_t)e1;
+            (v8 + 1)[L.o] = (uint8_t)lut_sym1<kTab>(e1);
+            v8[o1] = (uint8_t)e2;
+            (v8 + 1)[o1] = (uint8_t)lut_sym1<kTab>(e2);
+        }
+        out8[L.o] = (uint8_t)e1;
+        (out8 + 1)[L.o] = (uint8_t)lut_sym1<kTab>(e1);
+        out8[o1] = (uint8_t)e2;
+        (out8 + 1)[o1] = (uint8_t)lut_sym1<kTab>(e2);
+    }
+    L.o = o1 + (kTab == 3 ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2));
+    const uint32_t xn = L.X + u1 + u2;
+    const bool cross = (xn ^ L.X) > 31u;
+    L.d0 = cross ? L.d1 : L.d0;
+    L.d1 = cross ? L.d2 : L.d1;
+    L.d2 = cross ? d3 : L.d2;
+    L.X = xn;
+    if (u2 == 0u) {  // e2 holds no code (nor e1, if u1 == 0): a 13..30-bit code or EOS at X; > 12 bits are
+                     // left (>= kBodyMin - 12 before this lookup), so the leading-ones branch of lit12_step applies
+        const uint32_t wp = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
+        uint32_t sy, len;
+        bool eos;
+        lo_decode(wp, lo, sy, len, eos);
+        const uint32_t r = L.Eb - L.X;
+        if (len > r) {  // nothing fits in the > 12 bits left: huffman.rs:128-134
+            L.st = HPK_PADDING_TOO_LARGE;
+            L.Eb = L.X;
+        } else if (eos) {  // huffman.rs:112-116
+            L.st = HPK_EOS_IN_STRING;
+            L.Eb = L.X;
+        } else {
+            if (kStore != kNoStore) out8[L.o] = (uint8_t)sy;
+            L.o += 1;
+            L.X += len;
+            lit12_load(L, win32);
+        }
+    }
+    body = L.Eb - L.X >= kBodyMin;
+}
+
+// Final status of a literal whose walk has stopped; a status set by the walk wins.
+__device__ __forceinline__ uint32_t lit12_status(const Lit12& L) {
+    if (L.st != HPK_OK) return L.st;
+    return residual_status(L.Eb - L.X, __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X));
+}
+
+// ------------------------------------------------------------------------------------------
+// The code-by-code byte path: one literal decoded a code at a time into a byte destination with a
+// capacity check per byte (a literal whose output region is below the decoded bound).
+
+struct Lit {
+    uint64_t win;   // next bits, MSB-aligned (bits past the literal: whatever follows)
+    uint32_t nb;    // loaded bits in win
+    uint32_t nxt;   // next source dword (raw), merged at the next refill
+    uint32_t pf;    // the dword after it (raw, read one refill ahead)
+    uint32_t q;     // source dword index of pf
+    uint32_t rem;   // literal bits not yet consumed
+    uint32_t cnt;   // bytes decoded
+    uint32_t st;    // hpk_status
+    uint64_t acc;   // (unread since the dword stores went; with accn kept, zeroed in lit_begin, because the fill
+    uint32_t accn;  // kernel's diagnostic modes 2-4 allocate their registers differently without them)
+    bool live;      // still decoding
+};
+
+// Bitstream sources: a staged LDS window (big-endian dwords), or global memory (clamped to the batch).
+struct LdsSwapSrc {
+    const uint32_t* p;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return __builtin_bswap32(p[i]); }
+};
+struct GlobalSrc {
+    const uint32_t* p;
+    uint32_t last;  // last dword index holding a byte of the batch: never read past it
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return p[min(i, last)]; }
+};
+
+template <class Src>
+__device__ __forceinline__ void lit_begin(Lit& L, const Src& src, uint32_t sb, uint32_t nbytes) {
+    L.rem = nbytes * 8u;
+    L.cnt = 0;
+    L.st = HPK_OK;
+    L.live = nbytes != 0;
+    L.acc = 0;
+    L.accn = 0;
+    const uint32_t q0 = sb >> 2;
+    const uint32_t sk = (sb & 3u) * 8u;
+    const uint32_t d0 = src(q0);
+    L.nxt = src(q0 + 1);
+    L.pf = src(q0 + 2);
+    L.q = q0 + 2;
+    L.win = ((uint64_t)__builtin_bswap32(d0) << 32) << sk;
+    L.nb = 32u - sk;
+}
+
+// Top the window up to >= 32 bits from the prefetched dword; read the next one.
+template <class Src>
+__device__ __forceinline__ void lit_refill(Lit& L, const Src& src) {
+    const bool need = L.nb <= 32u;
+    const uint64_t add = (uint64_t)__builtin_bswap32(L.nxt) << ((32u - L.nb) & 63u);
+    L.win |= need ? add : 0ull;
+    L.nb += need ? 32u : 0u;
+    L.nxt = need ? L.pf : L.nxt;
+    L.q += need ? 1u : 0u;
+    L.pf = src(L.q);
+}
+
+template <class Src, class Dst>
+__device__ __forceinline__ void lit_bytes_to(Lit& L, const Src& src, const uint16_t* lo, Dst dst, uint32_t ocap,
+                                             uint32_t sb, uint32_t nbytes) {
+    lit_begin(L, src, sb, nbytes);
+    while (L.live) {
+        lit_refill(L, src);
+        uint32_t sym, len;
+        bool eos;
+        lo_decode((uint32_t)(L.win >> 32), lo, sym, len, eos);
+        if (len > L.rem) break;
+        if (eos) {
+            L.st = HPK_EOS_IN_STRING;
+            break;
+        }
+        if (L.cnt >= ocap) {
+            L.st = HPK_OUTPUT_OVERFLOW;
+            break;
+        }
+        dst(L.cnt, (uint8_t)sym);
+        L.cnt += 1;
+        L.win <<= len;
+        L.nb -= len;
+        L.rem -= len;
+        L.live = L.rem != 0u;
+    }
+}
+
+__device__ __forceinline__ uint32_t lit_status(const Lit& L) {
+    uint32_t st = L.st;
+    if (st == HPK_OK && L.rem > 0) {
+        if (L.rem > 7) {
+            st = HPK_PADDING_TOO_LARGE;
+        } else {
+            const uint32_t w = (uint32_t)(L.win >> 32) | (0xFFFFFFFFu >> L.rem);
+            if (w != 0xFFFFFFFFu) st = HPK_INVALID_PADDING;
+        }
+    }
+    return st;
+}
+
+}  // namespace hpkdec

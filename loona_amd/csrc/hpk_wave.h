@@ -30,16 +30,14 @@
 //     check per byte by the lane that holds it, after the lane loop (HPK_OUTPUT_OVERFLOW);
 //   * bad offsets stop the wave (HPK_BAD_OFFSETS for the rest of its range) and, through an LDS flag
 //     read at every fill, the workgroup's other waves at their next fill.
-// Semantics are huffman.rs:95-161 through lit12_step (hpk_decode12.h).
+// Semantics are huffman.rs:95-161 through the lane walk (hpk_walk.h).
 #pragma once
 #include <type_traits>
 
-#include "hpk_decode12.h"
+#include "hpk_decode_kernel.h"
+#include "hpk_huge.h"
+#include "hpk_long.h"
 
-
-#ifndef HPK_BODY
-#define HPK_BODY 1  // v27: unchecked body steps + checked tails (0: v26's checked steps throughout)
-#endif
 #ifndef HPK_BODY_UNROLL
 #define HPK_BODY_UNROLL 4  // body steps between the checks for a lane whose literal's body ended (2: config 5 +2.5 %)
 #endif
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
     uint32_t* s_ctr = reinterpret_cast<uint32_t*>(smem + G::kCtrOff);
     uint32_t* s_huge = s_ctr + 16;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    constexpr int kTab = HPK_LUT3 && HPK_BODY ? 3 : 2;  // the table layout of the fills and the phases after them
+    constexpr int kTab = HPK_LUT3 ? 3 : 2;  // the table layout of the fills and the phases after them
     const uint32_t BA = (uint32_t)((uint64_t)a.n * blockIdx.x / gridDim.x);
     const uint32_t BB = (uint32_t)((uint64_t)a.n * (blockIdx.x + 1) / gridDim.x);
     // (round 6) The start's memory round trips overlapped: every wave's first chunk is fixed here (wave wv's
@@ -403,7 +401,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
         uint32_t cur = cur0, ce = ce0;  // the first chunk (above)
         given = true;
         uint32_t gin = 0, gout = 0;
-        uint32_t sens[4] = {0u, 1u, 2u, 3u};  // diagnostic modes 6 / 7 only
+        uint32_t sens[4] = {0u, 1u, 2u, 3u};  // diagnostic mode 6 only
         if (cur < ce) {
             gin = gin0 + a.in_mis;
             gout = (kCompact ? ulay(cur, gin0) : gout0) + a.out_mis;
@@ -754,14 +752,12 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 T.prog = false;
                 lit12_load(T, wl32);
             };
-            load(L, e1, t1);
-            if (!(kMode != 1 && HPK_BODY)) load(N, e2, t2);  // (v28 loads the second literal when it starts)
-            bool nv = t2 < kq;
+            load(L, e1, t1);  // (the second literal is loaded when it starts, v28)
             uint32_t sX = 0, sO = 0, sSt = 0;
             bool s1 = false;
             stamp(5);
             uint32_t Lend = 0;  // the second walk's output end (bytes, image-relative)
-            if (kMode != 1 && HPK_BODY) {
+            if (kMode != 1) {
                 // v27: body steps (lit12_body, no fit tests) while a literal has >= kBodyMin bits left,
                 // slot t1's body then slot t2's; then the checked steps (lit12_step) for the two
                 // literals' last bits, t1's tail then t2's. A lane's first literal waits between the
@@ -777,7 +773,9 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                         if (body)
                             lit12_body<kStore, kTab, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(L, wl32, s_lut, s_lo, ol8,
                                                                                                    body);
-                        if (kMode == 6) {
+                        if (kMode == 6) {  // sensitivity diagnostic: 16 independent VALU per step (4 chains of
+                                           // 4) off the walk's dependency chain; the kernel's response says
+                                           // whether VALU issue binds
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[0]) : "v"(L.X));
@@ -821,54 +819,16 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                     if (L.more) lit12_step<kStore, true, kTab, true>(L, wl32, s_lut, s_lo, ol8, dmy);
                     if (N.more) lit12_step<kStore, true, kTab, true>(N, wl32, s_lut, s_lo, ol8, dmy);
                 }
-                // results in the v26 form: the first slot's end state saved, the second in L
+                // results: the first slot's end state saved, the second in L
                 sX = L.X;
                 sO = L.o;
                 sSt = L.st;
                 s1 = L.act;
                 L = N;
                 Lend = L.o;
-            } else if (kMode != 1) {
-                for (;;) {
-                    dg_add(9, 1u);
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        lit12_step<kStore, true>(L, wl32, s_lut, s_lo, ol8, dmy);
-                        // sensitivity diagnostics (libhpk_diag.so): mode 6 adds 16 independent VALU per
-                        // step (4 chains of 4), mode 7 adds 2 conflict-free LDS reads per step, off the
-                        // walk's dependency chain; the kernel's response says which resource binds
-                        if (kMode == 6) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[0]) : "v"(L.X));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[1]) : "v"(L.o));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[2]) : "v"(L.Eb));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[3]) : "v"(L.d1));
-                            }
-                        } else if (kMode == 7) {
-                            const uint32_t r1 = reinterpret_cast<volatile uint32_t*>(smem)[lane];
-                            const uint32_t r2 = reinterpret_cast<volatile uint32_t*>(smem)[64u + lane];
-                            sens[0] += r1 ^ r2;
-                        }
-                    }
-                    const bool fin = !L.prog;  // no progress in the last step: ended (a fixed point) or idle
-                    if (__any(fin)) {
-                        const bool sw = fin & nv;
-                        if (sw) {
-                            sX = L.X;
-                            sO = L.o;
-                            sSt = L.st;
-                            s1 = L.act;
-                            L = N;
-                            nv = false;
-                        }
-                        if (!__any(!fin | sw)) break;
-                    }
-                }
-                Lend = L.o;
             }
             stamp(6);
-            if ((kMode == 6 || kMode == 7) && (kMode == 7 ? sens[0] : sens[0] ^ sens[1] ^ sens[2] ^ sens[3]) == 0x5EB51u)
+            if (kMode == 6 && (sens[0] ^ sens[1] ^ sens[2] ^ sens[3]) == 0x5EB51u)
                 a.status[0] = 9u;  // (never: keeps the diagnostic work alive)
             // results: the first slot's from its saved end state, the second's from the walk
             {

@@ -140,7 +140,7 @@ def scatter_decode_gather(shards, decode_fn, group=None, root=0, device=None, co
     decode_fn(blob, off) -> (out_blob, out_off, out_len int32/uint32, status uint8) on `device`.
     compacted: decode_fn is the compacted form (HuffmanCodec.decode_compact, hpk_decode_batch_compact):
     literal i's bytes are at out_off[i] (starts, not regions: not monotone), and out_blob[:out_off[m]] is
-    the span the decode wrote. With the wave-fill kernel (batches of >= 4M literals) that span holds
+    the span the decode wrote. With the wave-fill kernel (every auto or wave batch) that span holds
     unwritten gaps between its workgroups' shares (~1.3x the decoded bytes on a config-5 shard), so the
     owner gathers the decoded bytes end to end exactly as for the region form (`compact` takes any
     per-literal starts) and only decoded bytes travel; root's offsets are their exclusive sum either way.

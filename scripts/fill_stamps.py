@@ -2,7 +2,7 @@
 """Per-wave phase stamps of the workgroup-fill decode kernel (diagnostic build, HPK_DEBUG_MODE=3,
 HPK_DECODE_KERNEL=fill) on a small batch, where a call's time is the kernel's fixed chain rather
 than its work: `python scripts/fill_stamps.py [literals]`. One JSON line: the kernel's event time and
-the mean / max s_memtime cycles per wave of each phase (hpk_decode12.h, mode 3)."""
+the mean / max s_memtime cycles per wave of each phase (hpk_fill.h, mode 3)."""
 import ctypes
 import json
 import os

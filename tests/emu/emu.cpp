@@ -1,13 +1,15 @@
-// Host emulation of decode v28's per-lane code with the REAL functions of loona_amd/csrc (extracted
-// by tests/emu/extract.py; tests/emu/shim.h stands in for the HIP builtins), against the oracle:
+// Host emulation of decode v28's per-lane code with the REAL functions of loona_amd/csrc (hpk_walk.h and
+// hpk_huge_piece.h, included as they are; tests/emu/shim.h stands in for the HIP builtins), against the oracle:
 //   1. the wave kernel's lane protocol (hpk_wave.h): body steps (lit12_body) for a lane's first
 //      literal, then its second, then both tails with checked steps that stop once a step proves the
 //      end (lit12_step<.., kMore>), LUT3 and LUT2 layouts, exact-bound regions back to back, lanes in
 //      reverse order (a stray byte past a region would hit an already decoded neighbour);
-//   2. the fill kernel's protocol (hpk_decode12.h: LUT2, no second-byte offset stores);
-//   3. the huge-literal phase (hpk_huge.h): its per-piece functions under the workgroup's protocol.
+//   2. the fill kernel's protocol (hpk_fill.h: LUT2, no second-byte offset stores);
+//   3. the huge-literal phase (hpk_huge.h): its per-piece functions (hpk_huge_piece.h) under the workgroup's protocol.
 // Test infrastructure only (tests/test_walk_emulation.py). Exit status 0 = no mismatch.
-#include "walk.h"
+#include "shim.h"
+#include "hpk_walk.h"
+#include "hpk_huge_piece.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,7 +17,6 @@
 #include <vector>
 extern "C" int oracle_decode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len);
 extern "C" int oracle_encode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_len);
-emu_dim3 threadIdx, blockIdx;
 using namespace hpkdec;
 
 static hpk_tables T;
