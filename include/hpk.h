@@ -139,6 +139,44 @@ int hpk_decode_batch_compact(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap
                              uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
                              uint8_t* status, int flags);
 
+/* ---- batch decode, packed output: the decoded bytes end to end, in literal order ------------
+ * The reference hands each literal back as an exact-length Vec (huffman.rs:98, 160); this form gives
+ * what those Vecs would be, concatenated: on return out_off (n+1 entries, an OUTPUT) is the exclusive
+ * sum of out_len (out_off[0] = 0, non-decreasing, out_off[n] = the decoded total), literal i's bytes are
+ * out_blob[out_off[i] .. out_off[i+1]) with no gap and no slack, and the blob can be sent, copied to the
+ * host or sliced as it is. status[i] and out_len[i] are exactly hpk_decode_batch's (an error literal
+ * keeps the bytes decoded before its error).
+ * out_cap may be any size (the caller does not know the total in advance; hpk_decoded_bound(in_cap)
+ * always suffices). No byte of out_blob at or past out_off[n] is written and nothing outside
+ * [out_blob, out_blob + out_cap). If out_off[n] > out_cap the bytes below out_cap are written, the rest
+ * are not, and out_off, out_len and status are still complete: a synchronous call then returns
+ * HPK_E_NOSPACE; after an HPK_ASYNC call the caller compares out_off[n] with its capacity itself.
+ * Bad offsets as hpk_decode_batch (status HPK_BAD_OFFSETS with out_len 0, the sticky flag, HPK_E_INVAL
+ * from the synchronous call, which wins over HPK_E_NOSPACE). n == 0 writes out_off[0] = 0.
+ * Device pointers only (HPK_PTR_DEVICE, optionally HPK_ASYNC); hpk_decoded_bound(in_cap) + 4 n must not
+ * pass HPK_MAX_OFFSET (HPK_E_INVAL, as the compacted form). Always the launch path: the small-call
+ * mode's persistent kernel does not answer it.
+ * How: the region decode (hpk_decode_batch's kernels, untouched) into scratch of the context, laid out
+ * by the literals' 4-rounded decoded bounds, then a scan of out_len and an ordered pack kernel that
+ * writes out_blob in whole aligned 16-byte chunks. The scratch is hpk_decoded_bound(in_cap) + 4 n bytes
+ * per stream the context is used on (grow-only, freed with the context): about 1.9 GB for a shard of
+ * 32M literals. */
+int hpk_decode_batch_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                            uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
+                            uint8_t* status, int flags);
+
+/* The pack step on its own, for results the caller already holds in the region or the compacted
+ * layout: literal i is src_blob[src_off[i] .. src_off[i] + src_len[i]); the starts may come in any
+ * order (n entries of src_off are read, so a region form's n+1 array can be passed as it is). Writes
+ * dst_off (n+1 entries: the exclusive sum of src_len) and the bytes end to end, dst_blob[dst_off[i] ..
+ * dst_off[i+1]) = literal i. Capacity, HPK_E_NOSPACE and what is left unwritten as
+ * hpk_decode_batch_packed. A literal with src_off[i] + src_len[i] > src_cap is a bad offset: it
+ * contributes length 0 and sets the sticky flag (HPK_E_INVAL from a synchronous call); so does every
+ * literal when the lengths' sum passes HPK_MAX_OFFSET. Nothing outside [src_blob, src_blob + src_cap)
+ * is read. Device pointers only (HPK_PTR_DEVICE, optionally HPK_ASYNC). */
+int hpk_pack_batch(hpk_ctx* ctx, const uint8_t* src_blob, size_t src_cap, const uint32_t* src_off,
+                   const uint32_t* src_len, uint32_t n, uint8_t* dst_blob, size_t dst_cap, uint32_t* dst_off, int flags);
+
 /* ---- batch encode --------------------------------------------------------
  * Symmetric: literal i = in_blob[in_off[i] .. in_off[i+1]) is Huffman-encoded
  * into out_blob[out_off[i] ..) with capacity out_off[i+1]-out_off[i]
@@ -359,6 +397,10 @@ void hpk_test_fail_batches(int n);
  * (n + 1 entries) into device memory out (n + 1 entries): the exclusive sum mod 2^32 of
  * (floor(8 len / 5) + 3) & ~3, synchronously on the context's stream. */
 int hpk_test_bound_scan(hpk_ctx* ctx, const uint32_t* in_off, uint32_t n, uint32_t* out);
+/* Testing only: the pack kernel's geometry: the bytes of a destination tile (a multiple of 16; tiles lie on
+ * 16-byte boundaries of the destination address) and how many literals' offsets a workgroup stages in
+ * LDS at a time. The tests place their edge cases relative to these. */
+int hpk_test_pack_geometry(uint32_t* tile_bytes, uint32_t* lds_literals);
 /* Testing only: how many decode calls of this context the small-call mode's persistent kernel has
  * answered (hpk_ctx_set_small_mode), so the tests can tell it ran. */
 uint64_t hpk_test_small_calls(const hpk_ctx* ctx);

@@ -49,6 +49,8 @@ EXPORTS = (
     "hpk_last_error",
     "hpk_decode_batch",
     "hpk_decode_batch_compact",
+    "hpk_decode_batch_packed",
+    "hpk_pack_batch",
     "hpk_encode_batch",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
@@ -81,6 +83,7 @@ EXPORTS = (
     "hpk_henc_out_free",
     "hpk_test_fail_batches",
     "hpk_test_bound_scan",
+    "hpk_test_pack_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
     "hpk_ctx_set_decode_kernel",
@@ -164,11 +167,19 @@ def lib() -> ctypes.CDLL:
         L.hpk_ctx_check.restype = ctypes.c_int
         L.hpk_last_error.argtypes = [ctypes.c_void_p]
         L.hpk_last_error.restype = ctypes.c_char_p
-        for fn in (L.hpk_decode_batch, L.hpk_encode_batch, L.hpk_decode_batch_compact):
+        batch_fns = [L.hpk_decode_batch, L.hpk_encode_batch, L.hpk_decode_batch_compact]
+        if hasattr(L, "hpk_decode_batch_packed"):  # (an A/B build of an older source has no packed form)
+            batch_fns.append(L.hpk_decode_batch_packed)
+        for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_int]
             fn.restype = ctypes.c_int
+        if hasattr(L, "hpk_pack_batch"):
+            L.hpk_pack_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p, ctypes.c_int]
+            L.hpk_pack_batch.restype = ctypes.c_int
         for fn in (L.hpk_decode_batch_cpu, L.hpk_encode_batch_cpu):
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
@@ -247,6 +258,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_bound_scan"):
             L.hpk_test_bound_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
             L.hpk_test_bound_scan.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_pack_geometry"):
+            L.hpk_test_pack_geometry.argtypes = [c_u32p, c_u32p]
+            L.hpk_test_pack_geometry.restype = ctypes.c_int
         L.hpk_version.argtypes = []
         L.hpk_version.restype = ctypes.c_char_p
         _lib = L

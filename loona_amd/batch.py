@@ -306,6 +306,67 @@ class HuffmanCodec:
                    out_len, status, True, sync)
         return out_blob, out_off, out_len, status
 
+    def decode_packed(self, in_blob, in_off, out_blob=None, out_off=None, out_len=None, status=None, sync=False):
+        """hpk_decode_batch_packed: torch cuda tensors -> (out_blob, out_off, out_len, status) with the decoded
+        bytes end to end in literal order, what the reference's exact-length Vecs (huffman.rs:98, 160) would
+        be, concatenated: out_off (n + 1 entries, an output) is the exclusive sum of out_len, literal i is
+        out_blob[out_off[i] : out_off[i + 1]] and out_off[n] the decoded total; status and out_len as
+        decode_device. out_blob may have any capacity: the bytes below it are written, and a synchronous call
+        raises (HPK_E_NOSPACE) when out_off[n] passes it; after an async call compare out_off[n] yourself.
+        out_blob=None allocates hpk_decoded_bound(in_blob) bytes, which always suffice, and with sync=True
+        the blob comes back cut to out_blob[:total] (the one host read of out_off[n]; not made otherwise)."""
+        import torch
+
+        n = int(in_off.shape[0]) - 1
+        dev = in_blob.device
+        need = compact_capacity(int(in_blob.numel()), n)
+        own = out_blob is None
+        if own:
+            out_blob = torch.empty(max((8 * int(in_blob.numel())) // 5, 1), dtype=torch.uint8, device=dev)
+        if out_off is None:
+            out_off = torch.empty(n + 1, dtype=torch.int32 if need < 2**31 else torch.uint32, device=dev)
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        self._call(self._L.hpk_decode_batch_packed, "hpk_decode_batch_packed", in_blob, in_off, out_blob, out_off,
+                   out_len, status, True, sync)
+        if own and sync:
+            out_blob = out_blob[: int(out_off[n].item()) & 0xFFFFFFFF]
+        return out_blob, out_off, out_len, status
+
+    def pack(self, src_blob, src_off, src_len, dst_blob=None, dst_off=None, sync=False):
+        """hpk_pack_batch: n = len(src_len) pieces src_blob[src_off[i] : src_off[i] + src_len[i]] (torch cuda
+        tensors; the starts in any order, a region form's n + 1 offsets accepted as they are) laid end to end
+        -> (dst_blob, dst_off), dst_off (n + 1 entries) the exclusive sum of src_len. A piece that passes
+        src_blob counts 0 bytes and raises the sticky error. dst_blob=None allocates src_blob's size (the
+        pieces of a decode result never sum to more), cut to dst_blob[:total] when sync=True; capacity
+        rules as decode_packed."""
+        import torch
+
+        n = int(src_len.shape[0])
+        if n >= 2**31 - 1:
+            raise ValueError("too many pieces")
+        dev = self.device
+        ps, src_cap = _arg(src_blob, "src_blob", ("uint8",), 0, dev)
+        pso, _ = _arg(src_off, "src_off", _OFF_DTYPES, n, dev)
+        psl, _ = _arg(src_len, "src_len", _OFF_DTYPES, n, dev)
+        own = dst_blob is None
+        if own:
+            dst_blob = torch.empty(max(int(src_blob.numel()), 1), dtype=torch.uint8, device=src_blob.device)
+        if dst_off is None:
+            dst_off = torch.empty(n + 1, dtype=torch.int32 if int(dst_blob.numel()) < 2**31 else torch.uint32,
+                                  device=src_blob.device)
+        pd, dst_cap = _arg(dst_blob, "dst_blob", ("uint8",), 0, dev)
+        pdo, _ = _arg(dst_off, "dst_off", _OFF_DTYPES, n + 1, dev)
+        self._follow()
+        flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        rc = self._L.hpk_pack_batch(self._h, ps, src_cap, pso, psl, ctypes.c_uint32(n), pd, dst_cap, pdo, flags)
+        _lib.check(rc, "hpk_pack_batch")
+        if own and sync:
+            dst_blob = dst_blob[: int(dst_off[n].item()) & 0xFFFFFFFF]
+        return dst_blob, dst_off
+
     def encode_device(self, in_blob, in_off, out_off=None, out_blob=None, out_len=None, status=None, sync=False):
         import torch
 

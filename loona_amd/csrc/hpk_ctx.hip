@@ -171,6 +171,9 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
         (void)hipFree(c->cp_bound[j]);
         (void)hipFree(c->cp_tmp[j]);
         (void)hipFree(c->cp_cursor[j]);
+        (void)hipFree(c->pk_scratch[j]);
+        (void)hipFree(c->pk_bound[j]);
+        (void)hipFree(c->pk_tmp[j]);
         if (c->long_ev[j]) (void)hipEventDestroy(c->long_ev[j]);
     }
     for (int j = 0; j < hpk_ctx::kMaxChunks; ++j) {
@@ -517,6 +520,85 @@ extern "C" int hpk_decode_batch_compact(hpk_ctx* c, const uint8_t* in_blob, size
         return take_err(c);
     }
     return HPK_E_OK;
+}
+
+// The end of a packed call: a synchronous one waits, then reports bad offsets (HPK_E_INVAL) before a
+// result that did not fit (HPK_E_NOSPACE: dst_off[n] read back with the wait).
+static int packed_end(hpk_ctx* c, const uint32_t* dst_off_n, size_t dst_cap, int flags) {
+    if (flags & HPK_ASYNC) return HPK_E_OK;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, dst_off_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = take_err(c)) return rc;
+    if ((size_t)total > dst_cap) return hpk_set_err_msg("the packed bytes pass the output capacity", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The packed form (include/hpk.h): the region decode into the slot's scratch blob, laid out by the
+// 4-rounded decoded bounds (hpk_bound_scan), out_len and status straight to the caller's arrays; then
+// out_off = the exclusive sum of out_len and the ordered pack from the scratch to out_blob (hpk_pack.hip).
+// No existing kernel changes, and the persistent kernel is not asked (always the launch path).
+extern "C" int hpk_decode_batch_packed(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
+                                       uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
+                                       uint32_t* out_len, uint8_t* status, int flags) {
+    if (!c || !in_off || !out_off || (n && (!out_len || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the packed form takes device pointers only", HPK_E_INVAL);
+    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the packed form", HPK_E_INVAL);
+    const uint64_t need = (uint64_t)hpk_decoded_bound(in_cap > HPK_MAX_OFFSET ? HPK_MAX_OFFSET : in_cap) + 4ull * n;
+    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the packed form's output would pass 4 GiB", HPK_E_INVAL);
+    if (n && (!in_blob || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
+        return packed_end(c, out_off, out_cap, flags);
+    }
+    int rc, j;
+    uint32_t* ll = nullptr;
+    if ((rc = hpk_long_list(c, n, &ll, &j))) return rc;  // (the slot hpk_launch_decode takes again below)
+    size_t tmp = 0;
+    if ((rc = hpk_bound_scan(c, in_off, n, nullptr, nullptr, &tmp))) return rc;
+    if (tmp < hpk_pack_tmp_bytes(n)) tmp = hpk_pack_tmp_bytes(n);  // (the two scans follow each other)
+    const size_t scratch = (size_t)need + 64;
+    if (c->pk_bound_cap[j] < ((size_t)n + 1) * 4 || c->pk_tmp_cap[j] < tmp || c->pk_scratch_cap[j] < scratch) {
+        if ((rc = hpk_slot_drain(c, j))) return rc;
+        if ((rc = grow((void**)&c->pk_bound[j], &c->pk_bound_cap[j], ((size_t)n + 1) * 4))) return rc;
+        if ((rc = grow(&c->pk_tmp[j], &c->pk_tmp_cap[j], tmp))) return rc;
+        if ((rc = grow((void**)&c->pk_scratch[j], &c->pk_scratch_cap[j], scratch))) return rc;
+    }
+    tmp = c->pk_tmp_cap[j];
+    if ((rc = hpk_bound_scan(c, in_off, n, c->pk_bound[j], c->pk_tmp[j], &tmp))) return rc;
+    const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, c->pk_scratch[j], (uint32_t)need, c->pk_bound[j], out_len,
+                      status};
+    if ((rc = hpk_launch_decode(c, b))) return rc;
+    if ((rc = hpk_pack_launch(c, c->pk_scratch[j], (uint32_t)need, c->pk_bound[j], out_len, n, out_blob, clamp_cap(out_cap),
+                              out_off, c->pk_tmp[j], need)))
+        return rc;
+    if ((rc = hpk_long_list_used(c, j))) return rc;
+    return packed_end(c, out_off + n, out_cap, flags);
+}
+
+// The pack step on its own: results already held in the region or compacted layout, laid end to end.
+extern "C" int hpk_pack_batch(hpk_ctx* c, const uint8_t* src_blob, size_t src_cap, const uint32_t* src_off,
+                              const uint32_t* src_len, uint32_t n, uint8_t* dst_blob, size_t dst_cap, uint32_t* dst_off,
+                              int flags) {
+    if (!c || !dst_off || (n && (!src_off || !src_len))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the pack takes device pointers only", HPK_E_INVAL);
+    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the pack", HPK_E_INVAL);
+    if (n && ((!src_blob && src_cap) || (!dst_blob && dst_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc, j;
+    uint32_t* ll = nullptr;
+    if ((rc = hpk_long_list(c, n, &ll, &j))) return rc;  // (only the stream's slot is wanted)
+    const size_t tmp = hpk_pack_tmp_bytes(n);
+    if (c->pk_tmp_cap[j] < tmp) {
+        if ((rc = hpk_slot_drain(c, j))) return rc;
+        if ((rc = grow(&c->pk_tmp[j], &c->pk_tmp_cap[j], tmp))) return rc;
+    }
+    if ((rc = hpk_pack_launch(c, src_blob, clamp_cap(src_cap), src_off, src_len, n, dst_blob, clamp_cap(dst_cap), dst_off,
+                              c->pk_tmp[j], HPK_MAX_OFFSET)))
+        return rc;
+    if ((rc = hpk_long_list_used(c, j))) return rc;
+    return packed_end(c, dst_off + n, dst_cap, flags);
 }
 
 extern "C" int hpk_encode_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,

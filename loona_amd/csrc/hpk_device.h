@@ -63,6 +63,14 @@ struct hpk_ctx {
     void* cp_tmp[kLongSlots] = {};
     size_t cp_tmp_cap[kLongSlots] = {};
     uint32_t* cp_cursor[kLongSlots] = {};
+    // the packed form (hpk_decode_batch_packed, hpk_pack_batch): the region decode's scratch blob and its
+    // bound layout, and the scans' scratch, per slot in the same way, grow-only
+    uint8_t* pk_scratch[kLongSlots] = {};
+    size_t pk_scratch_cap[kLongSlots] = {};
+    uint32_t* pk_bound[kLongSlots] = {};
+    size_t pk_bound_cap[kLongSlots] = {};
+    void* pk_tmp[kLongSlots] = {};
+    size_t pk_tmp_cap[kLongSlots] = {};
     // the small-call mode (hpk_ctx_set_small_mode, hpk_persist.h): a persistent kernel of sm_wgs
     // workgroups on its own stream takes synchronous device-pointer batches of <= sm_max literals
     uint32_t sm_max = 0;
@@ -128,5 +136,12 @@ int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, 
 // stream; tmp == nullptr: *tmp_bytes = the scratch it needs.
 int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out, void* tmp, size_t* tmp_bytes);
 int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b);
+// The ordered pack (hpk_pack.hip), on the ctx stream: dst_off (n + 1 entries) = the exclusive sum of the n
+// lengths, a literal with src_off + src_len > src_cap counting 0 (sticky error flag), then literal i's bytes
+// src_blob[src_off[i] ..) to dst_blob[dst_off[i] ..), of which only those below dst_cap are written. tmp:
+// hpk_pack_tmp_bytes(n) bytes of device scratch; total_bound: an upper bound of dst_off[n] (it sizes the grid).
+size_t hpk_pack_tmp_bytes(uint32_t n);
+int hpk_pack_launch(hpk_ctx* c, const uint8_t* src_blob, uint32_t src_cap, const uint32_t* src_off, const uint32_t* src_len,
+                    uint32_t n, uint8_t* dst_blob, uint32_t dst_cap, uint32_t* dst_off, void* tmp, uint64_t total_bound);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

@@ -90,14 +90,24 @@ def compact_offsets(out_len, m):
     return off
 
 
-def compact(out_blob, out_off, out_len, m, total, chunk=1 << 28):
+def compact(out_blob, out_off, out_len, m, total, chunk=1 << 28, codec=None):
     """The decoded bytes of m literals (literal i at out_off[i], out_len[i] bytes: the region layout a
     decode writes) laid end to end: a uint8 tensor of `total` bytes on the same device. Built in
     pieces of ~`chunk` bytes so the index tensor stays bounded; the pieces' literal and byte bounds
-    come to the host in ONE read (total is known, so nothing else waits on the device)."""
+    come to the host in ONE read (total is known, so nothing else waits on the device).
+    codec: a HuffmanCodec on the tensors' (CUDA) device: its pack kernel (HuffmanCodec.pack) makes the
+    same bytes in one pass, with no index tensor and no host read."""
     import torch
 
     dev = out_blob.device
+    if codec is not None and out_blob.is_cuda:
+        res = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if total == 0 or m == 0:
+            return res[:0]
+        src_off = out_off[:m] if out_off.is_contiguous() else out_off[:m].contiguous()
+        src_len = out_len[:m] if out_len.is_contiguous() else out_len[:m].contiguous()
+        codec.pack(out_blob, src_off, src_len, dst_blob=res)
+        return res[:total]
     res = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     if total == 0 or m == 0:
         return res[:0]
