@@ -3,6 +3,8 @@
 #include <string.h>
 #include <sys/mman.h>
 
+#include <initializer_list>
+
 #include "hpk_device.h"
 
 #define HPK_VERSION "hpk 0.37 gfx950 decode v37 (every batch: wave fills, each wave with its own LDS window and image, longest-first queue, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 29 bits are left, then checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only)"
@@ -77,71 +79,77 @@ extern "C" hpk_ctx* hpk_ctx_create(int device) {
     return c;
 }
 
-// The long-literal list of a launch: one slot per stream (a stream's launches are ordered, so its
-// slot is reused without a wait). Completion events are recorded only once a second stream has used
-// the context (an event record per launch cost ~1 us of a ~23 us small call); from then on a slot
-// taken over by another stream, or grown, waits for its last launch.
-int hpk_long_list(hpk_ctx* c, uint32_t n, uint32_t** list, int* slot) {
-    int j = -1;
+static int grow(void** p, size_t* cap, size_t need) {
+    if (need <= *cap) return HPK_E_OK;
+    size_t n = need + need / 4 + 4096;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(p, n));
+    *cap = n;
+    return HPK_E_OK;
+}
+
+// The per-stream slots: hpk_slot (hpk_device.h) has the rules these three keep.
+// slot_acquire: the slot of the context's current stream, claimed or taken over if it has none.
+static int slot_acquire(hpk_ctx* c, hpk_slot** slot) {
+    hpk_slot* s = nullptr;
     bool any = false;
-    for (int k = 0; k < hpk_ctx::kLongSlots; ++k) {
-        if (c->long_list[k] && c->long_stream[k] == c->stream) j = k;
-        any |= c->long_list[k] != nullptr;
+    for (hpk_slot& k : c->slots) {
+        if (k.used && k.stream == c->stream) s = &k;
+        any |= k.used;
     }
-    if (j < 0) {
-        if (any && !c->long_multi) {  // a second stream: events from here on; the past is drained
-            // once, here. (Recording an event on each earlier slot's stream would touch a handle the
-            // caller may have destroyed since — a stream bound with hpk_ctx_set_stream, created and
-            // destroyed by the caller: ADVICE r3.) Launches on a stream the context does not own always
-            // record their slot's event (hpk_long_list_used), so the only slots without one were used on
-            // the context's own stream: waiting for that stream drains them.
-            // Only those slots' (absent) events are cleared: a slot used on another stream keeps its
-            // recorded event, which the own-stream wait does not cover.
-            c->long_multi = true;
+    if (!s) {
+        if (any && !c->slot_events) {  // a second stream: events from here on; the past is drained once,
+            // here. (Recording an event on each earlier slot's stream would touch a handle the caller may
+            // have destroyed since.) The only slots without an event were used on the own stream.
+            c->slot_events = true;
             HIP_TRY(hipStreamSynchronize(c->own));
-            for (int k = 0; k < hpk_ctx::kLongSlots; ++k)
-                if (c->long_stream[k] == c->own) c->long_ev_set[k] = false;
+            for (hpk_slot& k : c->slots)
+                if (k.stream == c->own) k.ev_set = false;
         }
-        j = 0;
-        while (j < hpk_ctx::kLongSlots && c->long_list[j]) ++j;
-        if (j == hpk_ctx::kLongSlots) {  // all taken: reuse the oldest once its last launch is done
-            j = c->long_next;
-            c->long_next = (j + 1) % hpk_ctx::kLongSlots;
-            if (c->long_ev_set[j]) HIP_TRY(hipEventSynchronize(c->long_ev[j]));
+        int j = 0;
+        while (j < hpk_ctx::kSlots && c->slots[j].used) ++j;
+        if (j == hpk_ctx::kSlots) {  // all taken: the oldest, once its last launch is done
+            j = c->slot_next;
+            c->slot_next = (j + 1) % hpk_ctx::kSlots;
+            if (c->slots[j].ev_set) HIP_TRY(hipEventSynchronize(c->slots[j].ev));
         }
-        c->long_stream[j] = c->stream;
+        s = &c->slots[j];
+        s->stream = c->stream;
     }
-    if (c->long_multi && !c->long_ev[j]) HIP_TRY(hipEventCreateWithFlags(&c->long_ev[j], hipEventDisableTiming));
-    if (c->long_list_cap[j] < (size_t)n || !c->long_list[j]) {  // grow: the old list may still be in use
-        if (int rc = hpk_slot_drain(c, j)) return rc;
-        (void)hipFree(c->long_list[j]);
-        c->long_list[j] = nullptr;
-        c->long_list_cap[j] = 0;
-        const size_t cap = (size_t)n + (n >> 2) + 1024;
-        HIP_TRY(hipMalloc(&c->long_list[j], cap * sizeof(uint32_t)));
-        c->long_list_cap[j] = cap;
-    }
-    *list = c->long_list[j];
-    *slot = j;
+    if (c->slot_events && !s->ev) HIP_TRY(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    *slot = s;
     return HPK_E_OK;
 }
 
-int hpk_slot_drain(hpk_ctx* c, int j) {
-    if (c->long_ev_set[j])
-        HIP_TRY(hipEventSynchronize(c->long_ev[j]));
-    else if (c->long_list[j])  // a slot without an event was last used on the own stream (foreign
-                               // streams always record theirs): wait for that stream, not the caller's
-        HIP_TRY(hipStreamSynchronize(c->own));
+// slot_reserve: the buffers a call is about to use, each of at least its bytes. If any must grow, the
+// slot's last launch is waited for first (once), through its event or else the own stream.
+struct slot_need {
+    DevBuf* buf;
+    size_t bytes;
+};
+static int slot_reserve(hpk_ctx* c, hpk_slot* s, std::initializer_list<slot_need> needs) {
+    bool small = false;
+    for (const slot_need& nd : needs) small |= nd.buf->cap < nd.bytes;
+    if (small) {
+        if (s->ev_set)
+            HIP_TRY(hipEventSynchronize(s->ev));
+        else if (s->used)
+            HIP_TRY(hipStreamSynchronize(c->own));
+        for (const slot_need& nd : needs)
+            if (int rc = grow(&nd.buf->p, &nd.buf->cap, nd.bytes)) return rc;
+    }
+    s->used = true;
     return HPK_E_OK;
 }
 
-int hpk_long_list_used(hpk_ctx* c, int slot) {
-    if (!c->long_multi && c->stream == c->own) return HPK_E_OK;
-    // a stream the context does not own always gets its event: the slot is then never waited on
-    // through the stream handle, which the caller may destroy
-    if (!c->long_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&c->long_ev[slot], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->long_ev[slot], c->stream));
-    c->long_ev_set[slot] = true;
+// slot_commit: after the call's last operation on the stream, the slot's event recorded there.
+static int slot_commit(hpk_ctx* c, hpk_slot* s) {
+    if (!c->slot_events && c->stream == c->own) return HPK_E_OK;
+    if (!s->ev) HIP_TRY(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s->ev, c->stream));
+    s->ev_set = true;
     return HPK_E_OK;
 }
 
@@ -165,16 +173,11 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     (void)hipFree(c->d_st);
     if (c->h_err) (void)hipHostFree(c->h_err);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
-    for (int j = 0; j < hpk_ctx::kLongSlots; ++j) {
-        if (c->long_ev_set[j]) (void)hipEventSynchronize(c->long_ev[j]);
-        if (c->long_list[j]) (void)hipFree(c->long_list[j]);
-        (void)hipFree(c->cp_bound[j]);
-        (void)hipFree(c->cp_tmp[j]);
-        (void)hipFree(c->cp_cursor[j]);
-        (void)hipFree(c->pk_scratch[j]);
-        (void)hipFree(c->pk_bound[j]);
-        (void)hipFree(c->pk_tmp[j]);
-        if (c->long_ev[j]) (void)hipEventDestroy(c->long_ev[j]);
+    for (hpk_slot& s : c->slots) {
+        if (s.ev_set) (void)hipEventSynchronize(s.ev);
+        for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp})
+            (void)hipFree(b->p);
+        if (s.ev) (void)hipEventDestroy(s.ev);
     }
     for (int j = 0; j < hpk_ctx::kMaxChunks; ++j) {
         if (c->ev_in[j]) (void)hipEventDestroy(c->ev_in[j]);
@@ -267,17 +270,6 @@ extern "C" int hpk_ctx_sync(hpk_ctx* c) {
     return HPK_E_OK;
 }
 
-static int grow(void** p, size_t* cap, size_t need) {
-    if (need <= *cap) return HPK_E_OK;
-    size_t n = need + need / 4 + 4096;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(p, n));
-    *cap = n;
-    return HPK_E_OK;
-}
-
 static int check_offsets(const uint32_t* off, uint32_t n, size_t cap) {
     for (uint32_t i = 0; i < n; ++i)
         if (off[i + 1] < off[i]) return hpk_set_err_msg("offsets must be non-decreasing", HPK_E_INVAL);
@@ -298,7 +290,23 @@ extern "C" int hpk_ctx_check(hpk_ctx* c) {
     return take_err(c);
 }
 
+// the end of a device-pointer call: an asynchronous one returns, a synchronous one waits and reports bad offsets
+static int call_end(hpk_ctx* c, int flags) {
+    if (flags & HPK_ASYNC) return HPK_E_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return take_err(c);
+}
+
 typedef int (*launch_fn)(hpk_ctx*, const hpk_batch&);
+
+// the region form's decode as a launch_fn: the stream's slot with its list, the launch, the slot used
+static int decode_region(hpk_ctx* c, const hpk_batch& b) {
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->long_list, 4 * (size_t)b.n}}))) return rc;
+    if ((rc = hpk_launch_decode(c, b, s->long_list.as<uint32_t>()))) return rc;
+    return slot_commit(c, s);
+}
 
 static uint32_t clamp_cap(size_t cap) { return cap > HPK_MAX_OFFSET ? HPK_MAX_OFFSET : (uint32_t)cap; }
 
@@ -414,18 +422,13 @@ static int run_batch(launch_fn fn, hpk_ctx* c, const uint8_t* in_blob, size_t in
         if (n == 0) return HPK_E_OK;
         if (!in_blob || !out_blob) return hpk_set_err_msg("null blob", HPK_E_INVAL);
         const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), out_off, out_len, status};
-        if (fn == hpk_launch_decode && !(flags & HPK_ASYNC) && c->sm_max) {  // the small-call mode
+        if (fn == decode_region && !(flags & HPK_ASYNC) && c->sm_max) {  // the small-call mode
             bool handled = false;
             if (int rc = hpk_persist_call(c, b, &handled)) return rc;
             if (handled) return HPK_E_OK;
         }
-        int rc = fn(c, b);
-        if (rc) return rc;
-        if (!(flags & HPK_ASYNC)) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            return take_err(c);
-        }
-        return HPK_E_OK;
+        if (int rc = fn(c, b)) return rc;
+        return call_end(c, flags);
     }
     int chunks;
     uint32_t cut[hpk_ctx::kMaxChunks + 1];
@@ -442,7 +445,7 @@ int hpk_decode_host_begin(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, con
                           uint8_t* out_blob, size_t out_cap, const uint32_t* out_off, uint32_t* out_len,
                           uint8_t* status, int* nchunks, uint32_t* cut) {
     HIP_TRY(hipSetDevice(c->device));
-    return host_begin(hpk_launch_decode, c, in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status,
+    return host_begin(decode_region, c, in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status,
                       true, nchunks, cut);
 }
 
@@ -458,8 +461,25 @@ int hpk_ctx_max_chunks() { return hpk_ctx::kMaxChunks; }
 extern "C" int hpk_decode_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
                                 uint8_t* out_blob, size_t out_cap, const uint32_t* out_off, uint32_t* out_len,
                                 uint8_t* status, int flags) {
-    return run_batch(hpk_launch_decode, c, in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status,
+    return run_batch(decode_region, c, in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status,
                      flags);
+}
+
+// The argument checks that the compacted form, the packed form and the pack share; `what` names the caller in
+// the messages. in_cap (the two decodes): *need = the bytes that hold every literal's 4-rounded decoded bound.
+static int check_call(const hpk_ctx* c, bool null_arg, int flags, uint32_t n, const char* what, const size_t* in_cap,
+                      uint64_t* need) {
+    auto inval = [&](const char* before, const char* after) {
+        return hpk_set_err_msg((std::string(before) + what + after).c_str(), HPK_E_INVAL);
+    };
+    if (!c || null_arg) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (!(flags & HPK_PTR_DEVICE)) return inval("the ", " takes device pointers only");
+    if (n >= 0x7FFFFFFFu) return inval("too many literals for the ", "");
+    if (in_cap) {
+        *need = (uint64_t)hpk_decoded_bound(clamp_cap(*in_cap)) + 4ull * n;
+        if (*need > HPK_MAX_OFFSET) return inval("the ", "'s output would pass 4 GiB");
+    }
+    return HPK_E_OK;
 }
 
 // The compacted form (include/hpk.h). The kernels' images keep bound-sized regions (a literal's decoded
@@ -470,56 +490,40 @@ extern "C" int hpk_decode_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_ca
 extern "C" int hpk_decode_batch_compact(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
                                         uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
                                         uint32_t* out_len, uint8_t* status, int flags) {
-    if (!c || !in_off || !out_off || (n && (!out_len || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
-    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the compacted form takes device pointers only", HPK_E_INVAL);
-    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the compacted form", HPK_E_INVAL);
-    const uint64_t need = (uint64_t)hpk_decoded_bound(in_cap > HPK_MAX_OFFSET ? HPK_MAX_OFFSET : in_cap) + 4ull * n;
-    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the compacted form's output would pass 4 GiB", HPK_E_INVAL);
+    uint64_t need;
+    if (int rc = check_call(c, !in_off || !out_off || (n && (!out_len || !status)), flags, n, "compacted form", &in_cap,
+                            &need))
+        return rc;
     if (out_cap < need) return hpk_set_err_msg("out_cap below hpk_decoded_bound(in_cap) + 4 n", HPK_E_INVAL);
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
-    } else {
-        if (!in_blob || !out_blob) return hpk_set_err_msg("null blob", HPK_E_INVAL);
-        // the stream's slot (two calls on two streams must not share the cursor, the bound
-        // layout or the scan's scratch), its buffers regrown only once its last launch has completed
-        int rc, j;
-        uint32_t* ll = nullptr;
-        if ((rc = hpk_long_list(c, n, &ll, &j))) return rc;
-        if (hpk_compact_wave(c, n)) {  // (the kernel makes its bound layout and writes out_off[n])
-            const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), nullptr, out_len,
-                              status};
-            if ((rc = hpk_launch_decode_compact(c, b, out_off, ll, nullptr, true))) return rc;
-            if ((rc = hpk_long_list_used(c, j))) return rc;
-            if (!(flags & HPK_ASYNC)) {
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                return take_err(c);
-            }
-            return HPK_E_OK;
-        }
-        size_t tmp = 0;
-        if ((rc = hpk_bound_scan(c, in_off, n, nullptr, nullptr, &tmp))) return rc;
-        if (c->cp_bound_cap[j] < ((size_t)n + 1) * 4 || c->cp_tmp_cap[j] < tmp || !c->cp_cursor[j]) {
-            if ((rc = hpk_slot_drain(c, j))) return rc;
-            if ((rc = grow((void**)&c->cp_bound[j], &c->cp_bound_cap[j], ((size_t)n + 1) * 4))) return rc;
-            if ((rc = grow(&c->cp_tmp[j], &c->cp_tmp_cap[j], tmp))) return rc;
-            if (!c->cp_cursor[j]) HIP_TRY(hipMalloc(&c->cp_cursor[j], 4));
-        }
-        tmp = c->cp_tmp_cap[j];
-        if ((rc = hpk_bound_scan(c, in_off, n, c->cp_bound[j], c->cp_tmp[j], &tmp))) return rc;
-        HIP_TRY(hipMemsetAsync(c->cp_cursor[j], 0, 4, c->stream));
-        const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), c->cp_bound[j], out_len,
-                          status};
-        if ((rc = hpk_launch_decode_compact(c, b, out_off, ll, c->cp_cursor[j], false))) return rc;
-        // the span written: the cursor
-        HIP_TRY(hipMemcpyAsync(out_off + n, c->cp_cursor[j], 4, hipMemcpyDeviceToDevice, c->stream));
-        if ((rc = hpk_long_list_used(c, j))) return rc;
+        return call_end(c, flags);
     }
-    if (!(flags & HPK_ASYNC)) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return take_err(c);
+    if (!in_blob || !out_blob) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    const bool wave = hpk_compact_wave(c, n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s))) return rc;
+    if (wave)
+        rc = slot_reserve(c, s, {{&s->long_list, 4 * (size_t)n}});
+    else
+        rc = slot_reserve(c, s, {{&s->long_list, 4 * (size_t)n}, {&s->cp_bound, 4 * ((size_t)n + 1)},
+                                 {&s->cp_tmp, hpk_bound_tmp_bytes(n)}, {&s->cp_cursor, 4}});
+    if (rc) return rc;
+    hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), nullptr, out_len, status};
+    uint32_t* cursor = nullptr;
+    if (!wave) {
+        b.out_off = s->cp_bound.as<uint32_t>();
+        cursor = s->cp_cursor.as<uint32_t>();
+        if ((rc = hpk_bound_scan(c, in_off, n, s->cp_bound.as<uint32_t>(), s->cp_tmp.p))) return rc;
+        HIP_TRY(hipMemsetAsync(cursor, 0, 4, c->stream));
     }
-    return HPK_E_OK;
+    if ((rc = hpk_launch_decode_compact(c, b, out_off, s->long_list.as<uint32_t>(), cursor, wave))) return rc;
+    if (!wave)  // the span written: the cursor
+        HIP_TRY(hipMemcpyAsync(out_off + n, cursor, 4, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = slot_commit(c, s))) return rc;
+    return call_end(c, flags);
 }
 
 // The end of a packed call: a synchronous one waits, then reports bad offsets (HPK_E_INVAL) before a
@@ -528,8 +532,7 @@ static int packed_end(hpk_ctx* c, const uint32_t* dst_off_n, size_t dst_cap, int
     if (flags & HPK_ASYNC) return HPK_E_OK;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, dst_off_n, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = take_err(c)) return rc;
+    if (int rc = call_end(c, flags)) return rc;
     if ((size_t)total > dst_cap) return hpk_set_err_msg("the packed bytes pass the output capacity", HPK_E_NOSPACE);
     return HPK_E_OK;
 }
@@ -541,39 +544,32 @@ static int packed_end(hpk_ctx* c, const uint32_t* dst_off_n, size_t dst_cap, int
 extern "C" int hpk_decode_batch_packed(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
                                        uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
                                        uint32_t* out_len, uint8_t* status, int flags) {
-    if (!c || !in_off || !out_off || (n && (!out_len || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
-    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the packed form takes device pointers only", HPK_E_INVAL);
-    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the packed form", HPK_E_INVAL);
-    const uint64_t need = (uint64_t)hpk_decoded_bound(in_cap > HPK_MAX_OFFSET ? HPK_MAX_OFFSET : in_cap) + 4ull * n;
-    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the packed form's output would pass 4 GiB", HPK_E_INVAL);
+    uint64_t need;
+    if (int rc = check_call(c, !in_off || !out_off || (n && (!out_len || !status)), flags, n, "packed form", &in_cap, &need))
+        return rc;
     if (n && (!in_blob || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
         return packed_end(c, out_off, out_cap, flags);
     }
-    int rc, j;
-    uint32_t* ll = nullptr;
-    if ((rc = hpk_long_list(c, n, &ll, &j))) return rc;  // (the slot hpk_launch_decode takes again below)
-    size_t tmp = 0;
-    if ((rc = hpk_bound_scan(c, in_off, n, nullptr, nullptr, &tmp))) return rc;
-    if (tmp < hpk_pack_tmp_bytes(n)) tmp = hpk_pack_tmp_bytes(n);  // (the two scans follow each other)
-    const size_t scratch = (size_t)need + 64;
-    if (c->pk_bound_cap[j] < ((size_t)n + 1) * 4 || c->pk_tmp_cap[j] < tmp || c->pk_scratch_cap[j] < scratch) {
-        if ((rc = hpk_slot_drain(c, j))) return rc;
-        if ((rc = grow((void**)&c->pk_bound[j], &c->pk_bound_cap[j], ((size_t)n + 1) * 4))) return rc;
-        if ((rc = grow(&c->pk_tmp[j], &c->pk_tmp_cap[j], tmp))) return rc;
-        if ((rc = grow((void**)&c->pk_scratch[j], &c->pk_scratch_cap[j], scratch))) return rc;
-    }
-    tmp = c->pk_tmp_cap[j];
-    if ((rc = hpk_bound_scan(c, in_off, n, c->pk_bound[j], c->pk_tmp[j], &tmp))) return rc;
-    const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, c->pk_scratch[j], (uint32_t)need, c->pk_bound[j], out_len,
-                      status};
-    if ((rc = hpk_launch_decode(c, b))) return rc;
-    if ((rc = hpk_pack_launch(c, c->pk_scratch[j], (uint32_t)need, c->pk_bound[j], out_len, n, out_blob, clamp_cap(out_cap),
-                              out_off, c->pk_tmp[j], need)))
+    size_t tmp = hpk_bound_tmp_bytes(n);  // (the two scans follow each other: one scratch)
+    if (tmp < hpk_pack_tmp_bytes(n)) tmp = hpk_pack_tmp_bytes(n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->long_list, 4 * (size_t)n}, {&s->pk_bound, 4 * ((size_t)n + 1)}, {&s->pk_tmp, tmp},
+                                  {&s->pk_scratch, (size_t)need + 64}})))
         return rc;
-    if ((rc = hpk_long_list_used(c, j))) return rc;
+    uint32_t* bound = s->pk_bound.as<uint32_t>();
+    uint8_t* scratch = s->pk_scratch.as<uint8_t>();
+    if ((rc = hpk_bound_scan(c, in_off, n, bound, s->pk_tmp.p))) return rc;
+    const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, scratch, (uint32_t)need, bound, out_len, status};
+    if ((rc = hpk_launch_decode(c, b, s->long_list.as<uint32_t>()))) return rc;
+    if ((rc = hpk_pack_launch(c, scratch, (uint32_t)need, bound, out_len, n, out_blob, clamp_cap(out_cap), out_off,
+                              s->pk_tmp.p, need)))
+        return rc;
+    if ((rc = slot_commit(c, s))) return rc;
     return packed_end(c, out_off + n, out_cap, flags);
 }
 
@@ -581,23 +577,16 @@ extern "C" int hpk_decode_batch_packed(hpk_ctx* c, const uint8_t* in_blob, size_
 extern "C" int hpk_pack_batch(hpk_ctx* c, const uint8_t* src_blob, size_t src_cap, const uint32_t* src_off,
                               const uint32_t* src_len, uint32_t n, uint8_t* dst_blob, size_t dst_cap, uint32_t* dst_off,
                               int flags) {
-    if (!c || !dst_off || (n && (!src_off || !src_len))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
-    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the pack takes device pointers only", HPK_E_INVAL);
-    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the pack", HPK_E_INVAL);
+    if (int rc = check_call(c, !dst_off || (n && (!src_off || !src_len)), flags, n, "pack", nullptr, nullptr)) return rc;
     if (n && ((!src_blob && src_cap) || (!dst_blob && dst_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
     HIP_TRY(hipSetDevice(c->device));
-    int rc, j;
-    uint32_t* ll = nullptr;
-    if ((rc = hpk_long_list(c, n, &ll, &j))) return rc;  // (only the stream's slot is wanted)
-    const size_t tmp = hpk_pack_tmp_bytes(n);
-    if (c->pk_tmp_cap[j] < tmp) {
-        if ((rc = hpk_slot_drain(c, j))) return rc;
-        if ((rc = grow(&c->pk_tmp[j], &c->pk_tmp_cap[j], tmp))) return rc;
-    }
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->pk_tmp, hpk_pack_tmp_bytes(n)}}))) return rc;
     if ((rc = hpk_pack_launch(c, src_blob, clamp_cap(src_cap), src_off, src_len, n, dst_blob, clamp_cap(dst_cap), dst_off,
-                              c->pk_tmp[j], HPK_MAX_OFFSET)))
+                              s->pk_tmp.p, HPK_MAX_OFFSET)))
         return rc;
-    if ((rc = hpk_long_list_used(c, j))) return rc;
+    if ((rc = slot_commit(c, s))) return rc;
     return packed_end(c, dst_off + n, dst_cap, flags);
 }
 

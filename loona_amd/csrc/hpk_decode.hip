@@ -111,163 +111,15 @@ extern "C" int hpk_debug_stamps(unsigned long long* host, size_t cap_entries) {
 }
 #endif
 
-namespace {
-// The compacted mode's bound layout: the exclusive sum over the n + 1 elements "the 4-rounded decoded
-// bound of literal i" (0 for i = n; sums mod 2^32), in two passes over in_off: per 4,096-element tile the
-// sum of its bounds, one workgroup scanning the tile sums, then every tile scanned again with its base
-// (reads 2 x 4 B and writes 4 B per literal; hipcub's scan over a transform iterator took 151 us per
-// 32M literals, round 5).
-constexpr uint32_t kScanT = 256, kScanK = 16, kScanTile = kScanT * kScanK;
-
-__device__ __forceinline__ uint32_t bound_of(uint32_t a, uint32_t b) {
-    const uint64_t nb = (uint64_t)(b - a);  // (decreasing offsets: the decode kernel reports them)
-    const uint64_t bd = ((nb * 8u) / 5u + 3u) & ~(uint64_t)3u;
-    return bd > 0x7FFFFFFFu ? 0x7FFFFFFFu : (uint32_t)bd;
-}
-
-// the tile's offsets into LDS (striped, coalesced), element j's bound = s[j + 1] - s[j] (0 past n)
-__device__ __forceinline__ void scan_load(const uint32_t* __restrict__ off, uint32_t n, uint32_t base, uint32_t* s) {
-    const uint32_t t = threadIdx.x;
-#pragma unroll
-    for (uint32_t k = 0; k < kScanK; ++k) {
-        const uint32_t j = base + t + kScanT * k;
-        s[t + kScanT * k] = j <= n ? off[j] : 0u;
-    }
-    if (t == 0) s[kScanTile] = base + kScanTile <= n ? off[base + kScanTile] : 0u;
-    __syncthreads();
-}
-
-// exclusive block scan of one value per thread (256 threads), total to *tot
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* s_w, uint32_t* tot) {
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) s_w[w] = x;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kScanT / 64u; ++q) {
-        pre += q < w ? s_w[q] : 0u;
-        all += s_w[q];
-    }
-    *tot = all;
-    return pre + x - v;
-}
-
-__global__ __launch_bounds__(kScanT) void bound_tile_sums(const uint32_t* __restrict__ off, uint32_t n,
-                                                          uint32_t* __restrict__ sums) {
-    __shared__ uint32_t s[kScanTile + 1];
-    __shared__ uint32_t s_w[kScanT / 64];
-    const uint32_t base = blockIdx.x * kScanTile, t = threadIdx.x;
-    scan_load(off, n, base, s);
-    uint32_t acc = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kScanK; ++k) {
-        const uint32_t l = t * kScanK + k;
-        acc += base + l < n ? bound_of(s[l], s[l + 1]) : 0u;
-    }
-    uint32_t tot;
-    (void)block_exscan(acc, s_w, &tot);
-    if (t == 0) sums[blockIdx.x] = tot;
-}
-
-// one workgroup: the tile sums' exclusive scan, in place
-__global__ __launch_bounds__(kScanT) void bound_sums_scan(uint32_t* __restrict__ sums, uint32_t nt) {
-    __shared__ uint32_t s_w[kScanT / 64];
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nt; b0 += kScanT * kScanK) {
-        const uint32_t t = threadIdx.x;
-        uint32_t v[kScanK], acc = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kScanK; ++k) {
-            const uint32_t j = b0 + t * kScanK + k;
-            v[k] = j < nt ? sums[j] : 0u;
-            acc += v[k];
-        }
-        uint32_t tot;
-        uint32_t x = carry + block_exscan(acc, s_w, &tot);
-#pragma unroll
-        for (uint32_t k = 0; k < kScanK; ++k) {
-            const uint32_t j = b0 + t * kScanK + k;
-            if (j < nt) sums[j] = x;
-            x += v[k];
-        }
-        carry += tot;
-        __syncthreads();  // (s_w reused)
-    }
-}
-
-__global__ __launch_bounds__(kScanT) void bound_tile_scan(const uint32_t* __restrict__ off, uint32_t n,
-                                                          const uint32_t* __restrict__ sums, uint32_t* __restrict__ out) {
-    __shared__ uint32_t s[kScanTile + 1];
-    __shared__ uint32_t s_w[kScanT / 64];
-    const uint32_t base = blockIdx.x * kScanTile, t = threadIdx.x;
-    scan_load(off, n, base, s);
-    uint32_t v[kScanK], acc = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kScanK; ++k) {
-        const uint32_t l = t * kScanK + k;
-        v[k] = base + l < n ? bound_of(s[l], s[l + 1]) : 0u;
-        acc += v[k];
-    }
-    uint32_t tot;
-    uint32_t x = sums[blockIdx.x] + block_exscan(acc, s_w, &tot);
-    __syncthreads();  // (every thread's bounds are read: the tile's offsets give way to its results)
-#pragma unroll
-    for (uint32_t k = 0; k < kScanK; ++k) {
-        s[t * kScanK + k] = x;
-        x += v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kScanK; ++k) {
-        const uint32_t j = base + t + kScanT * k;
-        if (j <= n) out[j] = s[t + kScanT * k];
-    }
-}
-}  // namespace
-
-int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out, void* tmp, size_t* tmp_bytes) {
-    const uint32_t nt = (uint32_t)(((uint64_t)n + 1u + kScanTile - 1u) / kScanTile);  // tiles over n + 1 elements
-    if (!out) {
-        *tmp_bytes = (size_t)nt * 4u;
-        return HPK_E_OK;
-    }
-    if (*tmp_bytes < (size_t)nt * 4u) return HPK_E_INVAL;
-    uint32_t* sums = static_cast<uint32_t*>(tmp);
-    hipLaunchKernelGGL(bound_tile_sums, dim3(nt), dim3(kScanT), 0, c->stream, in_off, n, sums);
-    hipLaunchKernelGGL(bound_sums_scan, dim3(1), dim3(kScanT), 0, c->stream, sums, nt);
-    hipLaunchKernelGGL(bound_tile_scan, dim3(nt), dim3(kScanT), 0, c->stream, in_off, n, (const uint32_t*)sums, out);
-    HIP_TRY(hipGetLastError());
-    return HPK_E_OK;
-}
-
-// (tests only) the bound layout of device offsets into device memory, synchronously
-extern "C" int hpk_test_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out) {
-    size_t tmp = 0;
-    int rc = hpk_bound_scan(c, in_off, n, nullptr, nullptr, &tmp);
-    if (rc) return rc;
-    void* t = nullptr;
-    HIP_TRY(hipMalloc(&t, tmp ? tmp : 4));
-    rc = hpk_bound_scan(c, in_off, n, out, t, &tmp);
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    (void)hipFree(t);
-    return rc ? rc : e == hipSuccess ? HPK_E_OK : HPK_E_DEVICE;
-}
-
 static void decode_args(hpk_ctx* c, const hpk_batch& b, DecodeArgs& a) {
-    const uintptr_t ip = (uintptr_t)b.in_blob;
-    a.in_base = (const uint8_t*)(ip & ~(uintptr_t)15);
-    a.in_mis = (uint32_t)(ip & 15);
+    const auto in = split16(b.in_blob);
+    const auto out = split16(b.out_blob);
+    a.in_base = in.base;
+    a.in_mis = in.mis;
     a.in_off = b.in_off;
     a.n = b.n;
-    const uintptr_t op = (uintptr_t)b.out_blob;
-    a.out_base = (uint8_t*)(op & ~(uintptr_t)15);
-    a.out_mis = (uint32_t)(op & 15);
+    a.out_base = out.base;
+    a.out_mis = out.mis;
     a.out_off = b.out_off;
     a.out_len = b.out_len;
     a.status = b.status;
@@ -348,16 +200,17 @@ int hpk_persist_call(hpk_ctx* c, const hpk_batch& b, bool* handled) {
     auto* h = static_cast<PersistCtl*>(c->h_sm);
     if (!c->sm_launched || __atomic_load_n(&h->alive, __ATOMIC_ACQUIRE) == 0u)
         if (int rc = persist_launch(c, c->sm_req)) return rc;
-    const uintptr_t ip = (uintptr_t)b.in_blob, op = (uintptr_t)b.out_blob;
-    h->in_base = (const uint8_t*)(ip & ~(uintptr_t)15);
-    h->out_base = (uint8_t*)(op & ~(uintptr_t)15);
+    const auto in = split16(b.in_blob);
+    const auto out = split16(b.out_blob);
+    h->in_base = in.base;
+    h->out_base = out.base;
     h->in_off = b.in_off;
     h->out_off = b.out_off;
     h->out_len = b.out_len;
     h->status = b.status;
     h->n = b.n;
-    h->in_mis = (uint32_t)(ip & 15);
-    h->out_mis = (uint32_t)(op & 15);
+    h->in_mis = in.mis;
+    h->out_mis = out.mis;
     h->in_cap = b.in_cap;
     h->out_cap = b.out_cap;
     const uint32_t k = ++c->sm_req;
@@ -405,13 +258,10 @@ int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, 
     return HPK_E_OK;
 }
 
-int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b) {
+int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b, uint32_t* long_list) {
     DecodeArgs a;
     decode_args(c, b, a);
-    uint32_t* ll = nullptr;
-    int lslot = 0;
-    if (int rc = hpk_long_list(c, b.n, &ll, &lslot)) return rc;
-    a.long_list = ll;
+    a.long_list = long_list;
     a.long_min = HPK_LONG_MIN;
     a.long_big = HPK_LONG_BIG;
 #ifdef HPK_DIAG
@@ -443,7 +293,7 @@ int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b) {
             default: hipLaunchKernelGGL((WAVE_KERNEL(0)), grid, block, 0, c->stream, a); break;
         }
         HIP_TRY(hipGetLastError());
-        return hpk_long_list_used(c, lslot);
+        return HPK_E_OK;
     }
     // modes 3 and 5 write per-wave entries (16 each) into a.dbg; mode 5 adds to them, so they start zeroed
     if (g_debug_mode == 3 || g_debug_mode == 5) {
@@ -480,5 +330,5 @@ int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b) {
         hipLaunchKernelGGL(DEC_KERNEL(0), grid, block, 0, c->stream, a);
 #endif
     HIP_TRY(hipGetLastError());
-    return hpk_long_list_used(c, lslot);
+    return HPK_E_OK;
 }

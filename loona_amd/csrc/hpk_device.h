@@ -1,4 +1,4 @@
-// hpk_device.h — shared between the device translation units of libhpk (context, decode, encode).
+// hpk_device.h — shared between the device translation units of libhpk (context, decode, encode, pack).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +8,56 @@
 #include "../../include/hpk.h"
 #include "hpk_code.h"
 #include "hpk_internal.h"
+
+// A blob pointer as the kernels take it: the 16-byte-aligned address at or below it and the bytes between.
+template <class T>
+struct hpk_split16 {
+    T* base;
+    uint32_t mis;
+};
+template <class T>
+inline hpk_split16<T> split16(T* p) {
+    const uintptr_t u = (uintptr_t)p;
+    return {(T*)(u & ~(uintptr_t)15), (uint32_t)(u & 15)};
+}
+
+// A grow-only device buffer.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// The scratch of the device-pointer calls on one stream. Calls on different streams may overlap, so each
+// stream that uses the context gets a slot of its own (two calls on two streams never share a list, a
+// layout or the cursor: ADVICE r4); a stream's calls are ordered, so its slot is reused without a wait.
+// A call takes its stream's slot (slot_acquire), sizes the buffers it uses (slot_reserve), launches, and
+// marks the slot used after its last operation on the stream (slot_commit), all in hpk_ctx.hip. The rules:
+//   * While only the context's own stream has used it, no event is created or recorded (an event record
+//     per launch cost about 1 us of a ~23 us small call).
+//   * The first use by a second stream switches to events. It synchronises the own stream once, and clears
+//     the event-set flag only of slots last used on the own stream: a slot used on another stream keeps
+//     its recorded event, which the own-stream wait does not cover.
+//   * A launch on a stream that the context does not own always records its slot's event.
+//   * A slot is waited for through its event, or through the own stream if it has none (by the rule above
+//     it was then last used there). It is never waited for through another stream's handle: the caller
+//     may have destroyed that stream.
+//   * With all slots taken, the oldest is reused round-robin once its event has completed.
+//   * A buffer is freed or regrown only after the slot is drained, and a call drains at most once.
+//   * hpk_ctx_destroy waits on the set events before it frees.
+struct hpk_slot {
+    hipStream_t stream = nullptr;  // the stream that holds it, if `used` (nullptr is also the legacy stream)
+    bool used = false;             // a call has reserved it: launches that read its buffers may be in flight
+    hipEvent_t ev = nullptr;       // created at the slot's first use once the context records events
+    bool ev_set = false;           // ev was recorded after the slot's last launch
+    DevBuf long_list;     // the decode kernels' long-literal list: one u32 per literal of the batch
+    // the workgroup-fill kernel's compacted form: the bound layout, the bound scan's scratch, the output cursor
+    DevBuf cp_bound, cp_tmp, cp_cursor;
+    // the packed form: the region decode's scratch blob and its bound layout, and the two scans' scratch (the
+    // pack alone uses only the last)
+    DevBuf pk_scratch, pk_bound, pk_tmp;
+};
 
 struct hpk_ctx {
     int device = 0;
@@ -43,34 +93,11 @@ struct hpk_ctx {
     // sticky error flag: host-mapped, written (plain store of 1) by a kernel that saw bad offsets
     uint32_t* h_err = nullptr;
     uint32_t* d_err = nullptr;
-    // the long-literal list per stream (calls on different streams may overlap): one u32 per
-    // literal of the batch, grow-only. A slot's event is recorded after the launch that used it; a
-    // slot taken over from another stream (or grown) is reused only once that event has completed,
-    // whatever became of the stream that recorded it.
-    static constexpr int kLongSlots = 8;
-    hipStream_t long_stream[kLongSlots] = {};
-    hipEvent_t long_ev[kLongSlots] = {};
-    bool long_ev_set[kLongSlots] = {};
-    uint32_t* long_list[kLongSlots] = {};
-    size_t long_list_cap[kLongSlots] = {};
-    int long_next = 0;
-    bool long_multi = false;  // more than one stream has used the context: slots carry events
-    // the compacted mode (hpk_decode_batch_compact): the fills' bound layout, the scan's scratch and the
-    // output cursor, per slot like the long-literal list (two calls on two streams never share them),
-    // grow-only
-    uint32_t* cp_bound[kLongSlots] = {};
-    size_t cp_bound_cap[kLongSlots] = {};
-    void* cp_tmp[kLongSlots] = {};
-    size_t cp_tmp_cap[kLongSlots] = {};
-    uint32_t* cp_cursor[kLongSlots] = {};
-    // the packed form (hpk_decode_batch_packed, hpk_pack_batch): the region decode's scratch blob and its
-    // bound layout, and the scans' scratch, per slot in the same way, grow-only
-    uint8_t* pk_scratch[kLongSlots] = {};
-    size_t pk_scratch_cap[kLongSlots] = {};
-    uint32_t* pk_bound[kLongSlots] = {};
-    size_t pk_bound_cap[kLongSlots] = {};
-    void* pk_tmp[kLongSlots] = {};
-    size_t pk_tmp_cap[kLongSlots] = {};
+    // the per-stream slots (hpk_slot above)
+    static constexpr int kSlots = 8;
+    hpk_slot slots[kSlots];
+    int slot_next = 0;        // the round-robin victim when all are taken
+    bool slot_events = false;  // more than one stream has used the context: slots carry events
     // the small-call mode (hpk_ctx_set_small_mode, hpk_persist.h): a persistent kernel of sm_wgs
     // workgroups on its own stream takes synchronous device-pointer batches of <= sm_max literals
     uint32_t sm_max = 0;
@@ -91,14 +118,6 @@ struct hpk_ctx {
 int hpk_persist_call(hpk_ctx* c, const struct hpk_batch& b, bool* handled);
 int hpk_persist_start(hpk_ctx* c);
 int hpk_persist_stop(hpk_ctx* c);
-
-// The long-literal list for the context's current stream, sized for n literals (allocated on
-// first use; HPK_E_OK or an error code); *slot is passed to hpk_long_list_used after the launch.
-int hpk_long_list(hpk_ctx* c, uint32_t n, uint32_t** list, int* slot);
-// Records the slot's event on the context's stream after the launch that reads the list.
-int hpk_long_list_used(hpk_ctx* c, int slot);
-// Waits until the slot's last launch has completed (before its buffers are freed or regrown).
-int hpk_slot_drain(hpk_ctx* c, int slot);
 
 // One batch call as the launchers see it: capacities clamped to HPK_MAX_OFFSET (offsets above
 // them are bad whatever the buffer size).
@@ -123,19 +142,20 @@ int hpk_set_err_msg(const char* what, int code);
         if (_e != hipSuccess) return hpk_set_err(#call, _e);     \
     } while (0)
 
-int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b);
-// The compacted mode, co_off the caller's output offsets, long_list the slot's long-literal list (the
-// caller took the slot with hpk_long_list and records it used after its last operation on the stream).
-// wave (hpk_compact_wave): the wave-fill kernel, which makes its bound layout from in_off itself and
-// writes co_off[n]; otherwise the workgroup-fill kernel, b.out_off the bound layout made by
-// hpk_bound_scan and cursor the (zeroed) output cursor.
+// The launchers enqueue on the ctx stream. long_list: the long-literal list of the caller's slot, b.n
+// entries (the caller acquired and reserved the slot, and commits it after its last operation).
+int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b, uint32_t* long_list);
+// The compacted mode, co_off the caller's output offsets. wave (hpk_compact_wave): the wave-fill kernel,
+// which makes its bound layout from in_off itself and writes co_off[n]; otherwise the workgroup-fill
+// kernel, b.out_off the bound layout made by hpk_bound_scan and cursor the (zeroed) output cursor.
 bool hpk_compact_wave(const hpk_ctx* c, uint32_t n);
 int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, uint32_t* long_list, uint32_t* cursor,
                               bool wave);
-// out[i] = sum over j < i of the 4-rounded decoded bound of literal j (n + 1 entries), on the ctx
-// stream; tmp == nullptr: *tmp_bytes = the scratch it needs.
-int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out, void* tmp, size_t* tmp_bytes);
 int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b);
+// The bound layout (hpk_pack.hip): out[i] = sum over j < i of the 4-rounded decoded bound of literal j, mod
+// 2^32 (n + 1 entries); tmp: hpk_bound_tmp_bytes(n) bytes of device scratch.
+size_t hpk_bound_tmp_bytes(uint32_t n);
+int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out, void* tmp);
 // The ordered pack (hpk_pack.hip), on the ctx stream: dst_off (n + 1 entries) = the exclusive sum of the n
 // lengths, a literal with src_off + src_len > src_cap counting 0 (sticky error flag), then literal i's bytes
 // src_blob[src_off[i] ..) to dst_blob[dst_off[i] ..), of which only those below dst_cap are written. tmp:

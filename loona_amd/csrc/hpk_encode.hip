@@ -637,11 +637,12 @@ static unsigned long long* g_eprof = nullptr;  // HPK_ENCODE_PROF=1: hpk_encode2
 
 int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b) {
     EncodeArgs a{b.in_blob, b.in_off, b.n, b.out_blob, b.out_off, b.out_len, b.status, c->d_codes};
-    const uintptr_t ip = (uintptr_t)b.in_blob, op = (uintptr_t)b.out_blob;
-    a.in_base = (const uint8_t*)(ip & ~(uintptr_t)15);
-    a.in_mis = (uint32_t)(ip & 15);
-    a.out_base = (uint8_t*)(op & ~(uintptr_t)15);
-    a.out_mis = (uint32_t)(op & 15);
+    const auto in = split16(b.in_blob);
+    const auto out = split16(b.out_blob);
+    a.in_base = in.base;
+    a.in_mis = in.mis;
+    a.out_base = out.base;
+    a.out_mis = out.mis;
     a.in_cap = b.in_cap;
     a.out_cap = b.out_cap;
     a.err = c->d_err;

@@ -3,12 +3,10 @@
 // what the reference's exact-length Vecs (huffman.rs:98, 160) would be, concatenated.
 //
 // Two steps on the context's stream:
-//   * the length scan: dst_off = the exclusive u32 sum of the n lengths (n + 1 entries), in three
-//     launches like the compacted form's bound scan (hpk_decode.hip): per 4,096-element tile its sum,
-//     one workgroup scanning the tile sums, every tile scanned again from its base. A literal that
-//     passes the source capacity counts 0 bytes (and sets the sticky error flag); the tile sums are
-//     64-bit, and a total past HPK_MAX_OFFSET makes every length count 0 (flag set), so dst_off is
-//     always non-decreasing and the pack below never meets a wrapped offset;
+//   * the length scan: dst_off = the exclusive u32 sum of the n lengths (n + 1 entries), the tiled scan
+//     of hpk_scan.h over LenElem. A literal that passes the source capacity counts 0 bytes (and sets the
+//     sticky error flag); the tile sums are 64-bit, and a total past HPK_MAX_OFFSET makes every offset 0
+//     (flag set), so dst_off is always non-decreasing and the pack below never meets a wrapped offset;
 //   * hpk_pack (per-thread code in hpk_pack.h): destination-centric. The destination, counted from its
 //     16-byte-aligned base, is cut into tiles of kPackTile bytes; a workgroup takes a contiguous run of
 //     tiles, finds its first literal by one binary search of dst_off, and from then on keeps a window
@@ -17,144 +15,100 @@
 //     holds is made in rounds). Each thread makes one aligned 16-byte chunk per tile and stores it
 //     whole; the partial chunks at a misaligned start, at dst_off[n] and at the capacity go bytewise.
 //     Bytes at or past min(dst_off[n], dst_cap) are never written.
+//
+// The bound scan lives here too (hpk_bound_scan, the same tiled scan over BoundElem): the region layout
+// the packed form decodes into before it packs, and the workgroup-fill kernel's compacted layout.
 #include "hpk_device.h"
 #include "hpk_pack.h"
+#include "hpk_scan.h"
 
 using namespace hpkpack;
 
 namespace {
-constexpr uint32_t kLenT = 256, kLenK = 16, kLenTile = kLenT * kLenK;
+using hpkscan::kK;
+using hpkscan::kT;
+using hpkscan::kTile;
 
-// literal i's length as the pack counts it: 0 when its bytes would pass the source capacity
-__device__ __forceinline__ uint32_t len_of(uint32_t off, uint32_t len, uint32_t cap, bool* bad) {
-    const bool ok = len == 0u || (off <= cap && len <= cap - off);
-    *bad |= !ok;
-    return ok ? len : 0u;
-}
+// The bound layout's element: the 4-rounded decoded bound of literal i from two neighbouring offsets,
+// clamped to 2^31 - 1; its sums are mod 2^32. The tile's offsets are staged in LDS (striped, coalesced), so
+// that each is read once: element l's bound = s[l + 1] - s[l] rounded.
+struct BoundElem {
+    const uint32_t* __restrict__ off;
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t x, uint32_t d) {
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// exclusive block scan of one value per thread (kLenT threads), the total to *tot
-template <class T>
-__device__ __forceinline__ T block_exscan(T v, T* s_w, T* tot) {
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    T x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        T y;
-        if constexpr (sizeof(T) == 8) y = shfl_up64(x, d); else y = (T)__shfl_up((int)x, d);
-        if (lane >= d) x += y;
+    static __device__ __forceinline__ uint32_t bound_of(uint32_t a, uint32_t b) {
+        const uint64_t nb = (uint64_t)(b - a);  // (decreasing offsets: the decode kernel reports them)
+        const uint64_t bd = ((nb * 8u) / 5u + 3u) & ~(uint64_t)3u;
+        return bd > 0x7FFFFFFFu ? 0x7FFFFFFFu : (uint32_t)bd;
     }
-    if (lane == 63u) s_w[w] = x;
-    __syncthreads();
-    T pre = 0, all = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kLenT / 64u; ++q) {
-        pre += q < w ? s_w[q] : (T)0;
-        all += s_w[q];
-    }
-    *tot = all;
-    return pre + x - v;
-}
-
-__global__ __launch_bounds__(kLenT) void pack_len_sums(const uint32_t* __restrict__ off, const uint32_t* __restrict__ len,
-                                                       uint32_t n, uint32_t cap, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t s_w[kLenT / 64];
-    const uint32_t base = blockIdx.x * kLenTile, t = threadIdx.x;
-    uint32_t o[kLenK], l[kLenK];
-#pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) {  // (all the loads first)
-        const uint32_t j = base + t + kLenT * k;
-        o[k] = j < n ? off[j] : 0u;
-        l[k] = j < n ? len[j] : 0u;
-    }
-    uint64_t acc = 0;
-    bool bad = false;
-#pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) acc += len_of(o[k], l[k], cap, &bad);
-    uint64_t tot;
-    (void)block_exscan<uint64_t>(acc, s_w, &tot);
-    if (t == 0) sums[blockIdx.x] = tot;
-}
-
-// one workgroup: the tile sums' exclusive scan, in place; sums[nt] = 1 when the total does not fit
-__global__ __launch_bounds__(kLenT) void pack_sums_scan(uint64_t* __restrict__ sums, uint32_t nt) {
-    __shared__ uint64_t s_w[kLenT / 64];
-    uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nt; b0 += kLenTile) {
+    __device__ __forceinline__ void tile(uint32_t n, uint32_t base, uint32_t* s, uint32_t (&v)[kK]) const {
         const uint32_t t = threadIdx.x;
-        uint64_t v[kLenK], acc = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < kLenK; ++k) {
-            const uint32_t j = b0 + t * kLenK + k;
-            v[k] = j < nt ? sums[j] : 0u;
-            acc += v[k];
+        for (uint32_t k = 0; k < kK; ++k) {
+            const uint32_t j = base + t + kT * k;
+            s[t + kT * k] = j <= n ? off[j] : 0u;
         }
-        uint64_t tot;
-        uint64_t x = carry + block_exscan<uint64_t>(acc, s_w, &tot);
+        if (t == 0) s[kTile] = base + kTile <= n ? off[base + kTile] : 0u;
+        __syncthreads();
 #pragma unroll
-        for (uint32_t k = 0; k < kLenK; ++k) {
-            const uint32_t j = b0 + t * kLenK + k;
-            if (j < nt) sums[j] = x;
-            x += v[k];
+        for (uint32_t k = 0; k < kK; ++k) {
+            const uint32_t l = t * kK + k;
+            v[k] = base + l < n ? bound_of(s[l], s[l + 1]) : 0u;
         }
-        carry += tot;
-        __syncthreads();  // (s_w reused)
     }
-    if (threadIdx.x == 0) sums[nt] = carry > (uint64_t)HPK_MAX_OFFSET ? 1u : 0u;
-}
+    __device__ __forceinline__ uint32_t tile_sum(uint32_t n, uint32_t base, uint32_t* s) const {
+        uint32_t v[kK], acc = 0;
+        tile(n, base, s, v);
+#pragma unroll
+        for (uint32_t k = 0; k < kK; ++k) acc += v[k];
+        return acc;
+    }
+};
 
-__global__ __launch_bounds__(kLenT) void pack_len_scan(const uint32_t* __restrict__ off, const uint32_t* __restrict__ len,
-                                                       uint32_t n, uint32_t cap, const uint64_t* __restrict__ sums,
-                                                       uint32_t nt, uint32_t* __restrict__ out, uint32_t* __restrict__ err) {
-    __shared__ uint32_t s[kLenTile];
-    __shared__ uint32_t s_w[kLenT / 64];
-    const uint32_t base = blockIdx.x * kLenTile, t = threadIdx.x;
-    if (sums[nt] != 0u) {  // the total passes u32 offsets: nothing is packed
+// The pack's element: piece i's length, 0 when its bytes would pass the source capacity (the sticky error
+// flag is then set, by the tile scan). A thread loads all its offsets and lengths before it uses any.
+struct LenElem {
+    const uint32_t* __restrict__ off;
+    const uint32_t* __restrict__ len;
+    uint32_t cap;
+    uint32_t* err;
+
+    // the thread's striped elements base + threadIdx.x + kT * k into w; true: one of them passes the capacity
+    __device__ __forceinline__ bool load(uint32_t n, uint32_t base, uint32_t (&w)[kK]) const {
+        uint32_t o[kK], l[kK];
 #pragma unroll
-        for (uint32_t k = 0; k < kLenK; ++k) {
-            const uint32_t j = base + t + kLenT * k;
-            if (j <= n) out[j] = 0u;
+        for (uint32_t k = 0; k < kK; ++k) {
+            const uint32_t j = base + threadIdx.x + kT * k;
+            o[k] = j < n ? off[j] : 0u;
+            l[k] = j < n ? len[j] : 0u;
         }
-        if (t == 0) *err = 1u;
-        return;
-    }
-    uint32_t o[kLenK], l[kLenK];
+        bool bad = false;
 #pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) {  // (striped, coalesced; all the loads first)
-        const uint32_t j = base + t + kLenT * k;
-        o[k] = j < n ? off[j] : 0u;
-        l[k] = j < n ? len[j] : 0u;
+        for (uint32_t k = 0; k < kK; ++k) {
+            const bool ok = l[k] == 0u || (o[k] <= cap && l[k] <= cap - o[k]);
+            bad |= !ok;
+            w[k] = ok ? l[k] : 0u;
+        }
+        return bad;
     }
-    bool bad = false;
+    __device__ __forceinline__ void tile(uint32_t n, uint32_t base, uint32_t* s, uint32_t (&v)[kK]) const {
+        const uint32_t t = threadIdx.x;
+        uint32_t w[kK];
+        if (load(n, base, w)) *err = 1u;
 #pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) s[t + kLenT * k] = len_of(o[k], l[k], cap, &bad);
-    if (bad) *err = 1u;
-    __syncthreads();
-    uint32_t v[kLenK], acc = 0;
+        for (uint32_t k = 0; k < kK; ++k) s[t + kT * k] = w[k];
+        __syncthreads();
 #pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) {
-        v[k] = s[t * kLenK + k];
-        acc += v[k];
+        for (uint32_t k = 0; k < kK; ++k) v[k] = s[t * kK + k];
     }
-    uint32_t tot;
-    uint32_t x = (uint32_t)sums[blockIdx.x] + block_exscan<uint32_t>(acc, s_w, &tot);
-    __syncthreads();  // (every thread's lengths are read: they give way to the results)
+    __device__ __forceinline__ uint64_t tile_sum(uint32_t n, uint32_t base, uint32_t*) const {
+        uint32_t w[kK];
+        (void)load(n, base, w);
+        uint64_t acc = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) {
-        s[t * kLenK + k] = x;
-        x += v[k];
+        for (uint32_t k = 0; k < kK; ++k) acc += w[k];
+        return acc;
     }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kLenK; ++k) {
-        const uint32_t j = base + t + kLenT * k;
-        if (j <= n) out[j] = s[t + kLenT * k];
-    }
-}
+};
 
 struct PackArgs {
     PackSrc src;
@@ -230,35 +184,46 @@ __global__ __launch_bounds__(kPackThreads) void hpk_pack(PackArgs a) {
 }
 }  // namespace
 
-size_t hpk_pack_tmp_bytes(uint32_t n) {
-    const size_t nt = ((size_t)n + 1u + kLenTile - 1u) / kLenTile;
-    return (nt + 1u) * 8u;
+size_t hpk_bound_tmp_bytes(uint32_t n) { return hpkscan::tmp_bytes<uint32_t>(n); }
+
+int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out, void* tmp) {
+    hpkscan::launch<uint32_t>(c->stream, BoundElem{in_off}, n, out, tmp, nullptr);
+    HIP_TRY(hipGetLastError());
+    return HPK_E_OK;
 }
+
+// (tests only) the bound layout of device offsets into device memory, synchronously
+extern "C" int hpk_test_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out) {
+    void* t = nullptr;
+    HIP_TRY(hipMalloc(&t, hpk_bound_tmp_bytes(n)));
+    const int rc = hpk_bound_scan(c, in_off, n, out, t);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    (void)hipFree(t);
+    return rc ? rc : e == hipSuccess ? HPK_E_OK : HPK_E_DEVICE;
+}
+
+size_t hpk_pack_tmp_bytes(uint32_t n) { return hpkscan::tmp_bytes<uint64_t>(n); }
 
 // dst_off = the exclusive sum of the n lengths (those passing src_cap counted 0), then the bytes end to
 // end into dst_blob's first min(dst_off[n], dst_cap) bytes. tmp: hpk_pack_tmp_bytes(n) of device scratch.
 // total_bound: no more than this many bytes can come out (it only sizes the grid).
 int hpk_pack_launch(hpk_ctx* c, const uint8_t* src_blob, uint32_t src_cap, const uint32_t* src_off, const uint32_t* src_len,
                     uint32_t n, uint8_t* dst_blob, uint32_t dst_cap, uint32_t* dst_off, void* tmp, uint64_t total_bound) {
-    const uint32_t nt = (uint32_t)(((uint64_t)n + 1u + kLenTile - 1u) / kLenTile);
-    uint64_t* sums = static_cast<uint64_t*>(tmp);
-    hipLaunchKernelGGL(pack_len_sums, dim3(nt), dim3(kLenT), 0, c->stream, src_off, src_len, n, src_cap, sums);
-    hipLaunchKernelGGL(pack_sums_scan, dim3(1), dim3(kLenT), 0, c->stream, sums, nt);
-    hipLaunchKernelGGL(pack_len_scan, dim3(nt), dim3(kLenT), 0, c->stream, src_off, src_len, n, src_cap,
-                       (const uint64_t*)sums, nt, dst_off, c->d_err);
+    hpkscan::launch<uint64_t>(c->stream, LenElem{src_off, src_len, src_cap, c->d_err}, n, dst_off, tmp, c->d_err);
     HIP_TRY(hipGetLastError());
     uint64_t bytes = total_bound < dst_cap ? total_bound : dst_cap;
     if (bytes == 0 || n == 0) return HPK_E_OK;
+    const auto src = split16(src_blob);
+    const auto dst = split16(dst_blob);
     PackArgs a;
-    const uintptr_t sp = (uintptr_t)src_blob, dp = (uintptr_t)dst_blob;
-    a.src.base = (const uint32_t*)(sp & ~(uintptr_t)15);
-    a.src.mis = (uint32_t)(sp & 15);
+    a.src.base = (const uint32_t*)src.base;
+    a.src.mis = src.mis;
     a.src.cap = src_cap;
     a.src_off = src_off;
     a.dst_off = dst_off;
     a.n = n;
-    a.dst_base = (uint8_t*)(dp & ~(uintptr_t)15);
-    a.dst_mis = (uint32_t)(dp & 15);
+    a.dst_base = dst.base;
+    a.dst_mis = dst.mis;
     a.dst_cap = dst_cap;
     // a workgroup takes a contiguous run of tiles: 8 workgroups per CU when there are tiles enough
     const uint64_t tiles = (bytes + 15u + kPackTile - 1u) / kPackTile;

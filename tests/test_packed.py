@@ -354,6 +354,121 @@ def test_pack_alone(codec):
     codec.check()
 
 
+def _pack_into_view(codec, src, starts, lens, cap, shift=5, raises=None):
+    """codec.pack (synchronous) of host pieces into a view of `cap` bytes between canaries ->
+    (dst_off as int64, the view's bytes, canaries intact)"""
+    dsrc = to_dev(src)
+    dso, dsl = to_dev(np.asarray(starts, np.uint32).view(np.int32)), to_dev(np.asarray(lens, np.uint32).view(np.int32))
+    big = torch.full((GUARD + shift + cap + GUARD,), CANARY, dtype=torch.uint8, device="cuda")
+    view = big[GUARD + shift : GUARD + shift + cap]
+    doff = torch.full((len(lens) + 1,), -1, dtype=torch.int32, device="cuda")
+    if raises is None:
+        codec.pack(dsrc, dso, dsl, dst_blob=view, dst_off=doff, sync=True)
+    else:
+        with pytest.raises(RuntimeError, match=raises):
+            codec.pack(dsrc, dso, dsl, dst_blob=view, dst_off=doff, sync=True)
+    torch.cuda.synchronize()
+    g = big.cpu().numpy()
+    intact = bool((g[: GUARD + shift] == CANARY).all() and (g[GUARD + shift + cap :] == CANARY).all())
+    return doff.cpu().numpy().view(np.uint32).astype(np.int64), g[GUARD + shift : GUARD + shift + cap], intact
+
+
+@pytest.mark.parametrize("n", [0, 1, 4095, 4096, 4097, 16_781_313])
+def test_length_scan(codec, request, n):
+    """hpk_pack_batch's dst_off across the scan's tile boundary (4,096 pieces) and past one workgroup of tile
+    sums (16,777,216 pieces): the numpy exclusive sum. Small sizes: lengths 0-40 with some zeros, gapped
+    sources, the bytes a numpy gather, the canaries intact. The large size: lengths 0-3, every piece at one
+    small offset of a small source, dst_off only."""
+    rng = np.random.default_rng(n + 61)
+    if n > 4097:
+        if request.node.callspec.params["codec"] != "wave":
+            pytest.skip("one kernel variant is enough for the large size")
+        lens = rng.integers(0, 4, n).astype(np.int64)
+        eoff = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=eoff[1:])
+        src = to_dev(rng.integers(0, 256, 16, dtype=np.uint8))
+        dso = torch.full((n,), 5, dtype=torch.int32, device="cuda")
+        dst = torch.empty(int(eoff[-1]), dtype=torch.uint8, device="cuda")
+        _, doff = codec.pack(src, dso, to_dev(lens.astype(np.int32)), dst_blob=dst, sync=True)
+        got = doff.cpu().numpy().view(np.uint32).astype(np.int64)
+        assert np.array_equal(got, eoff), np.nonzero(got != eoff)[0][:5]
+        return
+    lens = rng.integers(0, 41, n).astype(np.int64)
+    if n:
+        lens[rng.integers(0, n, max(n // 50, 1))] = 0
+    starts = 5 + np.concatenate([[0], np.cumsum(lens + rng.integers(0, 9, n))[:-1]]).astype(np.int64)[:n]
+    src = rng.integers(0, 256, int(starts[-1] + lens[-1]) + 11 if n else 11, dtype=np.uint8)
+    flat, eoff = gather(src, starts, lens)
+    got, out, intact = _pack_into_view(codec, src, starts, lens, int(eoff[-1]))
+    assert np.array_equal(got, eoff), np.nonzero(got != eoff)[0][:5]
+    assert np.array_equal(out, flat)
+    assert intact
+
+
+@pytest.mark.parametrize("n", [4095, 4100])
+def test_length_scan_total_boundary(codec, n):
+    """Both sides of the 64-bit tile sums' limit, every piece the same 2^20 source bytes into a 4,096-byte
+    destination. 4,095 pieces total 4,293,918,720 <= HPK_MAX_OFFSET: dst_off exact, the first 4,096 bytes
+    packed, HPK_E_NOSPACE (-2). 4,100 pieces (two tiles) pass it: HPK_E_INVAL (-1), every dst_off entry 0
+    (include/hpk.h), nothing written, and the codec good afterwards."""
+    from loona_amd import _lib
+
+    rng = np.random.default_rng(71)
+    piece, cap = 1 << 20, 4096
+    src = rng.integers(0, 256, piece + 16, dtype=np.uint8)
+    starts, lens = np.zeros(n, np.int64), np.full(n, piece, np.int64)
+    total = n * piece
+    assert (total <= _lib.HPK_MAX_OFFSET) == (n == 4095)
+    if n == 4095:
+        got, out, intact = _pack_into_view(codec, src, starts, lens, cap, raises=r"hpk_pack_batch failed \(-2\)")
+        assert np.array_equal(got, np.arange(n + 1, dtype=np.int64) * piece)
+        assert np.array_equal(out, src[:cap])
+        assert intact
+        return
+    got, out, intact = _pack_into_view(codec, src, starts, lens, cap, raises=r"hpk_pack_batch failed \(-1\)")
+    assert not got.any(), np.nonzero(got)[0][:5]
+    assert (out == CANARY).all() and intact
+    codec.check()  # the failing synchronous call cleared the sticky flag
+    starts, lens = np.array([7, 100, 40]), np.array([9, 0, 30])
+    flat, eoff = gather(src, starts, lens)
+    got, out, intact = _pack_into_view(codec, src, starts, lens, int(eoff[-1]))
+    assert np.array_equal(got, eoff) and np.array_equal(out, flat) and intact
+
+
+def test_more_streams_than_slots(codec, request):
+    """The packed form and the pack alone on ten streams through one context, which has 8 per-stream slots:
+    a 300k-literal batch with long literals on the first stream, then nine 5k-literal batches on the others,
+    decode_packed alternating with decode_device + pack, all asynchronous. The ninth stream takes over the
+    first one's slot, whose scratch blob the large decode and pack may still be using. One synchronise, then
+    every result against the reference decode."""
+    from loona_amd import HuffmanCodec, synth
+
+    big = synth.device_config3(codec, n=300_000, seed=505)
+    small = [synth.device_config2(codec, n=5_000 + 211 * k, seed=600 + k) for k in range(9)]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream() for _ in range(10)]
+    res = []
+    with HuffmanCodec(0, stream="own") as c:
+        c.set_decode_kernel(request.node.callspec.params["codec"])
+        for k, w in enumerate([big] + small):
+            c.set_stream(streams[k])
+            if k % 2 == 0:
+                pb, po, pl, pst = c.decode_packed(w.enc_blob, w.enc_off)
+            else:
+                out, oo, pl, pst = c.decode_device(w.enc_blob, w.enc_off)
+                pb, po = c.pack(out, oo, pl[: w.n])
+            res.append((pb, po, pl, pst))
+        torch.cuda.synchronize()
+        c.check()
+        c.set_stream(torch.cuda.current_stream())
+    for k, (w, (pb, po, pl, pst)) in enumerate(zip([big] + small, res)):
+        flat, eoff, el, est = expected(w.enc_blob.cpu().numpy(), w.enc_off.cpu().numpy().view(np.uint32))
+        assert np.array_equal(po.cpu().numpy().view(np.uint32).astype(np.int64), eoff), f"call {k}: out_off"
+        assert np.array_equal(pl[: w.n].cpu().numpy().view(np.uint32), el), f"call {k}: out_len"
+        assert np.array_equal(pst[: w.n].cpu().numpy(), est), f"call {k}: status"
+        assert np.array_equal(pb.cpu().numpy()[: len(flat)], flat), f"call {k}: bytes"
+
+
 def test_shard_compact_with_codec(codec):
     """shard.compact(codec=...) equals shard.compact without it, on a region-form and a compacted-form result."""
     from loona_amd import shard, synth
