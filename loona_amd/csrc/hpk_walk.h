@@ -14,6 +14,9 @@
 //     (huffman.rs:128-160) looks at the residual bits only.
 //   * Stores (v14): a checked step's (up to) four byte stores are unconditional, a byte that is not
 //     output going to the lane's dummy slot (no exec-mask branch around each ds_write_b8).
+//   * Masked tail (v38, the wave kernel): a literal's last <= 28 bits in four lookups on the bits with
+//     ones past the literal's end, no fit test per code (lit12_tail, below); the checked step stays for
+//     the lanes it leaves as slow and for the other kernels.
 #pragma once
 #include <stdint.h>
 
@@ -320,6 +323,79 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
         }
     }
     body = L.Eb - L.X >= kBodyMin;
+}
+
+// Masked tail (decode v38): the last bits of a literal, rem = Eb - X <= 28 of them (0: an empty slot, or
+// a walk that ended in its body with a status), in straight-line code with no fit test per code and no
+// window read after lit12_load. The bits past the literal's end are set to ones: the stream then ends in
+// an all-ones run, which prefixes only EOS (30 bits), so for a valid literal plain lookups find exactly
+// the real codes and then "no code". Four lookups are enough: an entry holds a single code only when that
+// code and the next one take >= 13 bits together (an entry with two codes holds >= 10), so two lookups
+// that both hold a code consume >= 13 bits, four >= 26, and no code fits in the <= 2 bits then left; a
+// lookup that holds no code leaves the position where it is, and so do the lookups after it.
+//   * An entry is accepted while consumed + held <= rem: its codes then lie inside the literal, they are
+//     the codes the checked walk decodes, and their bytes go to o and o + 1. Every other byte (one the
+//     entry does not hold, or any byte of a rejected entry: a code completed by the ones past the end)
+//     goes to the lane's dummy slot, so a tail never stores outside the literal's region, whatever the
+//     input.
+//   * r = rem - consumed bits are left. A rejected entry (r wraps) or r >= 13 (a 13..28-bit code may
+//     start there and fit) makes the lane `slow`: its state is left as it was, and the caller runs the
+//     checked steps (lit12_step<.., kMore>) from it; the bytes already stored are the ones those steps
+//     store again. Otherwise no code fits in the r <= 12 bits left (a <= 12-bit code inside them would
+//     have been found), and the walk has ended: X moves there, st is the residual bits' status unless
+//     the body set one, and Eb = X (as after a status in the body: lit12_status then returns st).
+// The state lives inverted (n = ~bits: zeros past the end), so a shift by `held` fills with ones also
+// when held is 0 (v_alignbit_b32 by 32 - held would return the fill word). ~14 VALU, one table read and
+// two byte stores per lookup, against the ~48 / 2 / 4 of a checked step, of which a tail took two.
+struct Tail12 {
+    uint32_t n;     // ~(the 32 bits at X + used), zeros past the literal's end
+    uint32_t used;  // bits the lookups hold so far
+    uint32_t o;     // next output byte
+    uint32_t rem;   // bits left at the tail's start
+};
+
+__device__ __forceinline__ void tail12_begin(Tail12& T, const Lit12& L) {
+    T.rem = L.Eb - L.X;
+    T.n = ~__builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X) & ~(0xFFFFFFFFu >> T.rem);
+    T.used = 0;
+    T.o = L.o;
+}
+
+template <int kStore, int kTab>
+__device__ __forceinline__ void tail12_look(Tail12& T, const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8,
+                                            uint32_t dmy) {
+    const uint32_t e = lut[(T.n >> (32 - HPK_LUT_BITS)) ^ (HPK_LUT_SIZE - 1u)];
+    const uint32_t held = kTab == 3 ? HPK_L3_HELD(e) : HPK_L2_HELD(e);
+    T.used += held;
+    const uint32_t codes = T.used <= T.rem ? (kTab == 3 ? HPK_L3_CODES(e) : HPK_L2_CODES(e)) : 0u;
+    if (kStore != kNoStore) {
+        out8[codes >= 1u ? T.o : dmy] = (uint8_t)e;
+        (out8 + 1)[codes >= 2u ? T.o : dmy - 1u] = (uint8_t)lut_sym1<kTab>(e);
+    }
+    T.o += codes;
+    T.n <<= held;
+}
+
+// returns whether the lane is slow (L is then unchanged)
+__device__ __forceinline__ bool tail12_end(const Tail12& T, Lit12& L) {
+    const uint32_t r = T.rem - T.used;
+    const bool slow = r > (uint32_t)HPK_LUT_BITS;
+    const uint32_t st = r == 0u ? HPK_OK : (r > 7u ? HPK_PADDING_TOO_LARGE : (T.n != 0u ? HPK_INVALID_PADDING : HPK_OK));
+    L.X = slow ? L.X : L.X + T.used;
+    L.o = slow ? L.o : T.o;
+    L.st = slow || L.st != HPK_OK ? L.st : st;
+    L.Eb = slow ? L.Eb : L.X;
+    return slow;
+}
+
+template <int kStore, int kTab>
+__device__ __forceinline__ bool lit12_tail(Lit12& L, const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8,
+                                           uint32_t dmy) {
+    Tail12 T;
+    tail12_begin(T, L);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tail12_look<kStore, kTab>(T, lut, out8, dmy);
+    return tail12_end(T, L);
 }
 
 // Final status of a literal whose walk has stopped; a status set by the walk wins.

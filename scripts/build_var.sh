@@ -9,6 +9,7 @@ H="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 $H $FLAGS -x hip --offload-arch=gfx950 -c -o $T/dec.o hpk_decode.hip
 $H $FLAGS -x hip --offload-arch=gfx950 -c -o $T/ctx.o hpk_ctx.hip
 $H $FLAGS -x hip --offload-arch=gfx950 -c -o $T/enc.o hpk_encode.hip
+$H $FLAGS -x hip --offload-arch=gfx950 -c -o $T/pack.o hpk_pack.hip
 make -s hpk_cpu.o hpk_hpack.o hpk_h2.o
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libhpk_$NAME.so hpk_cpu.o hpk_hpack.o hpk_h2.o $T/ctx.o $T/dec.o $T/enc.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libhpk_$NAME.so hpk_cpu.o hpk_hpack.o hpk_h2.o $T/ctx.o $T/dec.o $T/enc.o $T/pack.o
 echo built loona_amd/libhpk_$NAME.so
