@@ -23,6 +23,10 @@
 #define HPK_EOS 256
 #define HPK_LUT_BITS 12
 #define HPK_LUT_SIZE (1u << HPK_LUT_BITS)
+// the wave kernel's two-symbol table: the LUT3 layout at 13 index bits (the pairs 6+7, 7+6, 5+8 and 8+5
+// of header text fit one entry; its fields hold 13: len0 <= 13 < 15, HPK_LUT2_CLAMP is 14)
+#define HPK_LUT13_BITS 13
+#define HPK_LUT13_SIZE (1u << HPK_LUT13_BITS)
 #define HPK_LO_RUNS 30
 #define HPK_LO_SIZE (HPK_LO_RUNS * 32)
 
@@ -92,6 +96,7 @@ struct hpk_tables {
     uint32_t lut[HPK_LUT_SIZE];
     uint32_t lut2[HPK_LUT_SIZE];
     uint32_t lut3[HPK_LUT_SIZE];
+    uint32_t lut13[HPK_LUT13_SIZE];  // LUT3 layout, HPK_LUT13_BITS-bit index
     uint16_t lo[HPK_LO_SIZE];
     uint8_t t8[256];  // symbol of the <=8-bit code that prefixes each 8-bit window (0 past LIM8)
 };
@@ -181,6 +186,34 @@ static inline int hpk_build_tables(hpk_tables* t) {
         const uint32_t e2 = t->lut2[v], codes = HPK_L2_CODES(e2);
         t->lut3[v] = (e2 & 0xFFu) | (HPK_L2_HELD(e2) << 8) | (e2 & 0x00FF0000u) | (codes << 24) |
                      ((codes ? HPK_L2_LEN0(e2) : 15u) << 26) | (codes < 2 ? HPK_L3_NOTTWO : 0u);
+    }
+    // LUT13: the LUT3 layout over HPK_LUT13_BITS index bits, built from the codes
+    for (uint32_t v = 0; v < HPK_LUT13_SIZE; ++v) {
+        const uint32_t w = v << (32 - HPK_LUT13_BITS);
+        int s0 = -1, l0 = 0, s1 = -1, l1 = 0;
+        for (int s = 0; s < 256; ++s) {
+            int L = t->len[s];
+            if (L <= HPK_LUT13_BITS && (w >> (32 - L)) == t->code[s]) { s0 = s; l0 = L; break; }
+        }
+        if (s0 < 0) {
+            t->lut13[v] = (15u << 26) | HPK_L3_NOTTWO;
+        } else {
+            const uint32_t w1 = w << l0;
+            const int rem = HPK_LUT13_BITS - l0;
+            for (int s = 0; s < 256 && rem >= 5; ++s) {
+                int L = t->len[s];
+                if (L <= rem && (w1 >> (32 - L)) == t->code[s]) { s1 = s; l1 = L; break; }
+            }
+            t->lut13[v] = (uint32_t)s0 | ((uint32_t)(l0 + l1) << 8) | ((uint32_t)(s1 < 0 ? 0 : s1) << 16) |
+                          ((s1 < 0 ? 1u : 2u) << 24) | ((uint32_t)l0 << 26) | (s1 < 0 ? HPK_L3_NOTTWO : 0u);
+        }
+        // against the 12-bit entry of the same bits: a first code of <= 12 bits is the same code; two codes
+        // there are the same two here; bits held never pass the index width
+        const uint32_t e = t->lut13[v], e3 = t->lut3[v >> 1];
+        if (HPK_L3_HELD(e) > HPK_LUT13_BITS) return -1;
+        if (HPK_L3_CODES(e3) == 2u && e != e3) return -1;
+        if (HPK_L3_CODES(e3) == 1u && ((e & 0xFFu) != (e3 & 0xFFu) || HPK_L3_LEN0(e) != HPK_L3_LEN0(e3))) return -1;
+        if (HPK_L3_CODES(e3) == 0u && HPK_L3_CODES(e) != 0u && HPK_L3_LEN0(e) != HPK_LUT13_BITS) return -1;
     }
     return 0;
 }

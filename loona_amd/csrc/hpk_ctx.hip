@@ -7,7 +7,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.38 gfx950 decode v38 (every batch: wave fills, each wave with its own LDS window and image, longest-first queue, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 29 bits are left, then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 13..28-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only)"
+#define HPK_VERSION "hpk 0.39 gfx950 decode v39 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, longest-first queue, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only)"
 
 static thread_local std::string t_last_error;
 
@@ -53,17 +53,16 @@ extern "C" hpk_ctx* hpk_ctx_create(int device) {
     c->num_cu = prop.multiProcessorCount;
     if ((e = hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
     c->stream = c->own;
-    if ((e = hipMalloc(&c->d_lut, sizeof(t->lut))) != hipSuccess) return fail("hipMalloc lut", e);
-    if ((e = hipMemcpy(c->d_lut, t->lut, sizeof(t->lut), hipMemcpyHostToDevice)) != hipSuccess) return fail("upload lut", e);
     if ((e = hipMalloc(&c->d_lut2, sizeof(t->lut2))) != hipSuccess) return fail("hipMalloc lut2", e);
     if ((e = hipMemcpy(c->d_lut2, t->lut2, sizeof(t->lut2), hipMemcpyHostToDevice)) != hipSuccess)
         return fail("upload lut2", e);
     if ((e = hipMalloc(&c->d_lut3, sizeof(t->lut3))) != hipSuccess) return fail("hipMalloc lut3", e);
     if ((e = hipMemcpy(c->d_lut3, t->lut3, sizeof(t->lut3), hipMemcpyHostToDevice)) != hipSuccess)
         return fail("upload lut3", e);
+    if ((e = hipMalloc(&c->d_lut13, sizeof(t->lut13))) != hipSuccess) return fail("hipMalloc lut13", e);
+    if ((e = hipMemcpy(c->d_lut13, t->lut13, sizeof(t->lut13), hipMemcpyHostToDevice)) != hipSuccess)
+        return fail("upload lut13", e);
     if ((e = hipMalloc(&c->d_lo, sizeof(t->lo))) != hipSuccess) return fail("hipMalloc lo", e);
-    if ((e = hipMalloc(&c->d_t8, sizeof(t->t8))) != hipSuccess) return fail("hipMalloc t8", e);
-    if ((e = hipMemcpy(c->d_t8, t->t8, sizeof(t->t8), hipMemcpyHostToDevice)) != hipSuccess) return fail("upload t8", e);
     if ((e = hipMalloc(&c->d_codes, 2 * 257 * sizeof(uint32_t))) != hipSuccess) return fail("hipMalloc codes", e);
     uint32_t packed[2 * 257];
     for (int s = 0; s < 257; ++s) {
@@ -161,11 +160,10 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     if (c->h_sm) (void)hipHostFree(c->h_sm);
     (void)hipFree(c->d_sm_dev);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_lut);
     (void)hipFree(c->d_lut2);
     (void)hipFree(c->d_lut3);
+    (void)hipFree(c->d_lut13);
     (void)hipFree(c->d_lo);
-    (void)hipFree(c->d_t8);
     (void)hipFree(c->d_codes);
     (void)hipFree(c->d_in);
     (void)hipFree(c->d_out);

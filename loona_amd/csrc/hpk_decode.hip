@@ -14,8 +14,9 @@
 //     one workgroup-wide fill at a time per CU (40 KiB window, 77 KiB image, 2048-literal
 //     longest-first queue), the next fill's loads in flight during the decode, the previous image
 //     written back around it.
-// Both use the same lane walk (hpk_walk.h): a step is two lookups in the 12-bit two-symbol
-// table, each decoding up to two codes of <= 12 bits, from a 32-bit window made by ONE v_alignbit
+// Both use the same lane walk (hpk_walk.h): a step is two lookups in the two-symbol table (13 index
+// bits in the wave kernel since v39, 12 in the workgroup-fill and the small-call kernel), each decoding
+// up to two codes within the index bits, from a 32-bit window made by ONE v_alignbit
 // out of a register-held dword pair; a longer code (or EOS) takes one leading-ones lookup. Bits past
 // a literal's end are not masked: a code that runs past the end is, by prefix-freeness, longer than
 // what is left whatever follows, so the walk stops exactly where huffman.rs's bit iterator stops
@@ -46,10 +47,17 @@ constexpr int kWaves = 16, kW = 40960, kO = 79104, kQ = 2048, kRefillN = 2;
 #define HPK_LONG_BIG 1024
 #endif
 using Geo = Geo12<kWaves, kW, kO, kQ>;
-// Wave-fill kernel (v25, hpk_wave.h): per wave a 3 KiB window and a 5.75 KiB image, the workgroup's
-// range handed out in chunks of 224 literals; it runs every batch (HPK_WAVE_MIN is 0) unless the context
-// forces the workgroup-fill kernel (hpk_ctx_set_decode_kernel)
-constexpr int kWaveWin = 3072, kWaveImg = 5888;
+// Wave-fill kernel (v25, hpk_wave.h): per wave a 3,008-byte window and a 5,040-byte image (v39: 8,048 bytes
+// per wave beside the 13-bit table; until v38 3,072 + 5,888, the image's last 256 the dummy slots), the
+// workgroup's range handed out in chunks of 224 literals; it runs every batch (HPK_WAVE_MIN is 0) unless the
+// context forces the workgroup-fill kernel (hpk_ctx_set_decode_kernel)
+#ifndef HPK_WAVE_WIN
+#define HPK_WAVE_WIN 3008  // (config 5: 2880 696.0-701.9, 3008 681.7-691.0, 3136 761.3-767.5 us: a fourth window round)
+#endif
+#ifndef HPK_WAVE_IMG
+#define HPK_WAVE_IMG (8048 - HPK_WAVE_WIN)
+#endif
+constexpr int kWaveWin = HPK_WAVE_WIN, kWaveImg = HPK_WAVE_IMG;
 #ifndef HPK_WAVE_MIN
 #define HPK_WAVE_MIN 0u  // least literals of a batch the wave kernel takes in HPK_DECODE_AUTO: every batch since round 6
                          // (it had been 4M: config 2 40.3-40.8 vs 47.1-47.3 us for the workgroup-fill kernel,
@@ -72,7 +80,8 @@ constexpr int kWaveWin = 3072, kWaveImg = 5888;
 #define HPK_WAVE_GUIDED_MIN 4000000u
 #endif
 #ifndef HPK_WAVE_SMALL_CHUNK
-#define HPK_WAVE_SMALL_CHUNK 96u  // (config 2: 88 43.1-43.5, 92 40.5-41.0, 96 40.3-40.6, 100 42.4-43.3, 104 43.3-43.9 us)
+#define HPK_WAVE_SMALL_CHUNK 96u  // (config 2: 88 43.1-43.5, 92 40.5-41.0, 96 40.3-40.6, 100 42.4-43.3, 104 43.3-43.9 us;
+                                  // v39, fills of ~108 literals: 92 36.5-37.0, 96 36.4-37.8, 100 38.1-38.4)
 #endif
 #define WAVE_KERNEL_SMALL(m) hpk_decode_wave<m, kWaveWin, kWaveImg, HPK_WAVE_SMALL_CHUNK, 2, HPK_WAVE_RANK>
 #define DEC_KERNEL(m) hpk_decode12<m, kWaves, kW, kO, kQ, kRefillN>
@@ -123,11 +132,10 @@ static void decode_args(hpk_ctx* c, const hpk_batch& b, DecodeArgs& a) {
     a.out_off = b.out_off;
     a.out_len = b.out_len;
     a.status = b.status;
-    a.t8 = c->d_t8;
     a.lo = c->d_lo;
-    a.lut = c->d_lut;
     a.lut2 = c->d_lut2;
     a.lut3 = c->d_lut3;
+    a.lut13 = c->d_lut13;
     a.dbg = nullptr;
     a.in_cap = b.in_cap;
     a.out_cap = b.out_cap;

@@ -11,8 +11,9 @@
 
 namespace hpkdec {
 
-// Tables in LDS (once per workgroup): T8 (256 B, symbols of the <= 8-bit codes) and the
-// leading-ones table LO (1.9 KiB, any code). 16-byte aligned carve-outs.
+// Tables in LDS (once per workgroup): the leading-ones table LO (1.9 KiB, any code), in the workgroup-fill
+// kernel behind 256 bytes that once held T8 (symbols of the <= 8-bit codes; nothing reads them, and that
+// kernel's LDS layout is left as it is; the wave kernel has no such carve-out). 16-byte aligned.
 constexpr int kT8Bytes = 256;
 constexpr int kLoBytes = HPK_LO_SIZE * 2;
 constexpr int kTabBytes = ((kT8Bytes + kLoBytes + 15) / 16) * 16;
@@ -27,11 +28,10 @@ struct DecodeArgs {
     const uint32_t* out_off;
     uint32_t* out_len;
     uint8_t* status;
-    const uint8_t* t8;
     const uint16_t* lo;
-    const uint32_t* lut;  // two-symbol table (hpk_code.h), step 8
-    const uint32_t* lut2; // the same in the LUT2 layout (decode v12)
-    const uint32_t* lut3; // the same in the LUT3 layout (decode v28, the wave kernel's long and huge phases)
+    const uint32_t* lut2;   // two-symbol table (hpk_code.h) in the LUT2 layout (decode v12, the workgroup-fill kernel)
+    const uint32_t* lut3;   // the same in the LUT3 layout (decode v28)
+    const uint32_t* lut13;  // the LUT3 layout at 13 index bits (decode v39: the wave kernel, its long and huge phases)
     unsigned long long* dbg;  // diagnostic builds only: per-wave timestamps
     uint32_t in_cap, out_cap;  // blob sizes (clamped to HPK_MAX_OFFSET): larger offsets are bad
     uint32_t* err;             // sticky error flag (host-mapped): set to 1 on bad offsets

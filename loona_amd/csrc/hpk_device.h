@@ -65,11 +65,10 @@ struct hpk_ctx {
     int decode_kernel = HPK_DECODE_AUTO;  // hpk_ctx_set_decode_kernel
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
-    uint32_t* d_lut = nullptr;
     uint32_t* d_lut2 = nullptr;
     uint32_t* d_lut3 = nullptr;
+    uint32_t* d_lut13 = nullptr;
     uint16_t* d_lo = nullptr;
-    uint8_t* d_t8 = nullptr;
     uint32_t* d_codes = nullptr;  // [0,257) code, [257,514) length
     // grow-only scratch for HPK_PTR_HOST calls
     uint8_t* d_in = nullptr;

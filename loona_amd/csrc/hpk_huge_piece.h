@@ -68,14 +68,14 @@ __device__ __forceinline__ void huge_peek(HugeWalk& W, const Ld& ld16, const uin
         }
     }
     const uint32_t w = (uint32_t)(W.win >> 32);
-    const uint32_t e = lut[w >> (32 - HPK_LUT_BITS)];
-    const uint32_t l0 = kTab == 3 ? HPK_L3_LEN0(e) : HPK_L2_LEN0(e);  // 15: no code of <= 12 bits
-    if (l0 <= (uint32_t)HPK_LUT_BITS) {
+    const uint32_t e = lut[w >> (32 - lut_bits<kTab>())];
+    const uint32_t l0 = lut_l3<kTab>() ? HPK_L3_LEN0(e) : HPK_L2_LEN0(e);  // 15: no code within the index bits
+    if (l0 <= lut_bits<kTab>()) {
         sym = e & 0xFFu;
         len = l0;
         eos = false;
-        const uint32_t codes = kTab == 3 ? HPK_L3_CODES(e) : HPK_L2_CODES(e);
-        held = codes == 2u ? (kTab == 3 ? HPK_L3_HELD(e) : HPK_L2_HELD(e)) : 0u;
+        const uint32_t codes = lut_l3<kTab>() ? HPK_L3_CODES(e) : HPK_L2_CODES(e);
+        held = codes == 2u ? (lut_l3<kTab>() ? HPK_L3_HELD(e) : HPK_L2_HELD(e)) : 0u;
         sym1 = (e >> 16) & 0xFFu;
     } else {
         lo_decode(w, lo, sym, len, eos);

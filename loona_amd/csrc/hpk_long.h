@@ -136,7 +136,9 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
     // front, so a period starts with <= 15 bytes and adds <= 5 per step: 15 + 5 kU + 3 bytes
     // (a step's 4-byte store) must fit.
     constexpr uint32_t kOS = kOSz;
-    // (HPK_LONG_TAILPT: a tail at the refill point adds <= 6 bytes: < kBodyMin bits, codes of >= 5 bits)
+    // (HPK_LONG_TAILPT: a tail at the refill point adds <= 6 bytes: < body_min <= 31 bits, codes of >= 5 bits;
+    // a body step adds <= 5 whatever the table's width: four codes of its two entries and a long one)
+    static_assert(body_min<kTab>() <= 35u, "a tail's bytes");
     static_assert(15 + 5 * kU + 3 + (HPK_LONG_TAILPT ? 6 : 0) < (int)kOS, "output buffer");
     static_assert((kRing & (kRing - 1)) == 0 && kRing >= 16 && 4 * kCh + 8 <= kRing, "input ring: a power of two >= 16 dwords");
     static_assert(kBlock % 64 == 0 && kBlock <= kBlockAll, "decoding waves");
@@ -202,23 +204,23 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
         // the ring: checked steps (lit12_step's) until the walk ends; the literal is finished in 4 below
         if (HPK_LONG_TAILPT) {
             for (;;) {
-                const bool tl = act && live && !done && Eb - X < kBodyMin && h * 4u >= span;
+                const bool tl = act && live && !done && Eb - X < body_min<kTab>() && h * 4u >= span;
                 if (!__any(tl)) break;
                 if (tl) {
                     const uint32_t j0 = X >> 5;
                     const uint32_t d3 = ring[((j0 + 2u) & (kRing - 1u)) * kBlock];
                     const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, ~X);
                     const uint32_t rem = Eb - X;
-                    const uint32_t e1 = s_lut[w >> (32 - HPK_LUT_BITS)];
+                    const uint32_t e1 = s_lut[w >> (32 - lut_bits<kTab>())];
                     bool a1, a2;
                     const uint32_t u1 = lut12<kTab>(e1, rem, a1, a2);
-                    bool park = !a1 & (rem > (uint32_t)HPK_LUT_BITS);
+                    bool park = !a1 & (rem > lut_bits<kTab>());
                     const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
                     const uint32_t rem2 = rem - u1;
-                    const uint32_t e2 = s_lut[(w << u1) >> (32 - HPK_LUT_BITS)];
+                    const uint32_t e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
                     bool b1, b2;
                     const uint32_t v2 = lut12<kTab>(e2, rem2, b1, b2);
-                    park |= cont & !b1 & (rem2 > (uint32_t)HPK_LUT_BITS);
+                    park |= cont & !b1 & (rem2 > lut_bits<kTab>());
                     b1 &= cont;
                     b2 &= cont;
                     const uint32_t g1 = (uint32_t)a1 + (uint32_t)a2, g2 = (uint32_t)b1 + (uint32_t)b2;
@@ -414,14 +416,14 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
             pend = true;
         }
         // ---- kU steps while the input ring holds what a step can reach: a step advances < 2 dwords
-        // (<= 24 bits of lookups + a <= 30-bit long code) and reads up to dword (X >> 5) + 3; the
+        // (<= 24 bits of lookups, 26 with the 13-bit table, + a <= 30-bit long code) and reads up to dword (X >> 5) + 3; the
         // lane's budget of steps is set here, not checked per step (config 3 936.7 vs 1026.9 us) ----
         const uint32_t x5 = X >> 5;
         const uint32_t budget = !(act && live) ? 0u
                                 : h * 4u >= span ? (uint32_t)kU
                                 : x5 + 4u <= h ? min((uint32_t)kU, ((h - x5 - 4u) >> 1) + 1u) : 0u;
         for (int s = 0; s < kU; ++s) {
-            const bool go = (uint32_t)s < budget && !done && (!HPK_LONG_TAILPT || Eb - X >= kBodyMin);
+            const bool go = (uint32_t)s < budget && !done && (!HPK_LONG_TAILPT || Eb - X >= body_min<kTab>());
             if (kDiag) {
                 dg[2] += (unsigned long long)__popcll(__ballot(go));
                 dg[3] += (unsigned long long)__popcll(__ballot(act && live && !done && !go));
@@ -436,28 +438,28 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
             const uint32_t rem = Eb - X;
             uint32_t e1, e2, u1, u2, g1, g2;
             bool park, prog;
-            if (HPK_LONG_TAILPT || (HPK_LONG_BODY && rem >= kBodyMin)) {
+            if (HPK_LONG_TAILPT || (HPK_LONG_BODY && rem >= body_min<kTab>())) {
                 // body step (lit12_body): every code of the two entries ends inside the literal
-                e1 = s_lut[w >> (32 - HPK_LUT_BITS)];
-                u1 = kTab == 3 ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
-                e2 = s_lut[(w << u1) >> (32 - HPK_LUT_BITS)];
-                u2 = kTab == 3 ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
-                g1 = kTab == 3 ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1);
-                g2 = kTab == 3 ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2);
-                park = u2 == 0u;  // (> 12 bits left at e2: kBodyMin - 12)
+                e1 = s_lut[w >> (32 - lut_bits<kTab>())];
+                u1 = lut_l3<kTab>() ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
+                e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
+                u2 = lut_l3<kTab>() ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
+                g1 = lut_l3<kTab>() ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1);
+                g2 = lut_l3<kTab>() ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2);
+                park = u2 == 0u;  // (more bits than the table's index left at e2: body_min less the index bits)
                 prog = true;
             } else {
-                e1 = s_lut[w >> (32 - HPK_LUT_BITS)];
+                e1 = s_lut[w >> (32 - lut_bits<kTab>())];
                 bool a1, a2;
                 u1 = lut12<kTab>(e1, rem, a1, a2);
-                park = !a1 & (rem > (uint32_t)HPK_LUT_BITS);  // (see lit12_step)
+                park = !a1 & (rem > lut_bits<kTab>());  // (see lit12_step)
                 const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
                 const uint32_t w2 = w << u1;
                 const uint32_t rem2 = rem - u1;
-                e2 = s_lut[w2 >> (32 - HPK_LUT_BITS)];
+                e2 = s_lut[w2 >> (32 - lut_bits<kTab>())];
                 bool b1, b2;
                 const uint32_t v2 = lut12<kTab>(e2, rem2, b1, b2);
-                park |= cont & !b1 & (rem2 > (uint32_t)HPK_LUT_BITS);
+                park |= cont & !b1 & (rem2 > lut_bits<kTab>());
                 b1 &= cont;
                 b2 &= cont;
                 g1 = (uint32_t)a1 + (uint32_t)a2;

@@ -5,7 +5,8 @@
 //   * Lane walk (v12): a lane holds its bit position as X = P + 31 and the dword pair (d0, d1) =
 //     window dwords (X >> 5) - 1 and X >> 5, plus the next dword d2. The 32 bits at P are ONE
 //     v_alignbit_b32(d0, d1, ~X). A step does two lookups in the two-symbol table (LUT2 / LUT3 layout,
-//     hpk_code.h), each decoding up to two codes of <= 12 bits, and advances <= 24 bits, so it crosses
+//     hpk_code.h; 12 index bits, or 13 in the wave kernel: lut_bits), each decoding up to two codes of <= 12
+//     (13) bits, and advances <= 24 (26) bits, so it crosses
 //     at most one dword: the pair then slides by one (v_cndmask) and d2 takes d3, the dword read at the
 //     top of the step. A code longer than 12 bits (EOS included) takes the rarely taken branch: one
 //     leading-ones lookup. Bits past a literal's end are never masked: a code that runs past the end is,
@@ -64,13 +65,27 @@ __device__ __forceinline__ uint32_t win_at(const uint32_t* __restrict__ win32, u
     return __builtin_amdgcn_alignbit(q[-1], q[0], ~x);
 }
 
+// The two-symbol table a walk reads, kTab (hpk_code.h): 2 = LUT2 and 3 = LUT3, both of HPK_LUT_BITS = 12
+// index bits; 4 = the LUT3 layout at HPK_LUT13_BITS = 13 index bits (decode v39, the wave kernel and its
+// phases). Everything that depends on the index width takes it from here.
+template <int kTab>
+constexpr uint32_t lut_bits() {
+    static_assert(kTab >= 2 && kTab <= 4, "table kind");
+    return kTab == 4 ? (uint32_t)HPK_LUT13_BITS : (uint32_t)HPK_LUT_BITS;
+}
+template <int kTab>
+constexpr bool lut_l3() {  // the entry layout is LUT3's
+    return kTab >= 3;
+}
+
 // The codes one table entry decodes with rem bits left: ok1 / ok2 = its first / second code fits
 // inside the literal; returns the bits they use.
-template <int kTab = 2>  // the table layout: 2 = LUT2, 3 = LUT3 (hpk_code.h)
+template <int kTab = 2>
 __device__ __forceinline__ uint32_t lut12(uint32_t e, uint32_t rem, bool& ok1, bool& ok2) {
     // a length field the entry does not hold is 15, past any clamped rem (and t1 >= l1: ok2 => ok1)
+    static_assert(lut_bits<kTab>() < HPK_LUT2_CLAMP, "a held length is below the clamp");
     const uint32_t rc = min(rem, HPK_LUT2_CLAMP);
-    if (kTab == 3) {
+    if (lut_l3<kTab>()) {
         const uint32_t l1 = HPK_L3_LEN0(e), t1 = HPK_L3_HELD(e);
         ok1 = l1 <= rc;
         ok2 = (t1 <= rc) & (e < HPK_L3_NOTTWO);
@@ -83,7 +98,7 @@ __device__ __forceinline__ uint32_t lut12(uint32_t e, uint32_t rem, bool& ok1, b
 }
 template <int kTab>
 __device__ __forceinline__ bool lut_nottwo(uint32_t e) {
-    return kTab == 3 ? e >= HPK_L3_NOTTWO : e >= HPK_LUT2_NOTTWO;
+    return lut_l3<kTab>() ? e >= HPK_L3_NOTTWO : e >= HPK_LUT2_NOTTWO;
 }
 // An entry's second symbol byte, in place for a byte store (LUT2 / LUT3: [23:16])
 template <int kTab>
@@ -144,13 +159,13 @@ __device__ __forceinline__ bool lit12_step_main(Lit12& L, const uint32_t* __rest
     const uint32_t d3 = win32[(L.X >> 5) + 2];  // the dword after d2, in case this step crosses one
     const uint32_t w = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
     const uint32_t rem = L.Eb - L.X;
-    const uint32_t e1 = lut[w >> (32 - HPK_LUT_BITS)];
+    const uint32_t e1 = lut[w >> (32 - lut_bits<kTab>())];
     bool a1, a2;
     const uint32_t u1 = lut12<kTab>(e1, rem, a1, a2);
     uint32_t use = u1;
     // a code longer than 12 bits (or EOS) starts here and may still fit (with more than 12 bits
     // left, any code the entry holds fits: no first code <=> the entry has none)
-    bool park = !a1 & (rem > (uint32_t)HPK_LUT_BITS);
+    bool park = !a1 & (rem > lut_bits<kTab>());
     bool more2 = false;
     if (kStore == kPred) {
         out8[a1 ? L.o : dmy] = (uint8_t)e1;
@@ -168,10 +183,10 @@ __device__ __forceinline__ bool lit12_step_main(Lit12& L, const uint32_t* __rest
         const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
         const uint32_t w2 = w << u1;
         const uint32_t rem2 = rem - u1;
-        const uint32_t e2 = lut[w2 >> (32 - HPK_LUT_BITS)];
+        const uint32_t e2 = lut[w2 >> (32 - lut_bits<kTab>())];
         bool b1, b2;
         const uint32_t u2 = lut12<kTab>(e2, rem2, b1, b2);
-        park |= cont & !b1 & (rem2 > (uint32_t)HPK_LUT_BITS);
+        park |= cont & !b1 & (rem2 > lut_bits<kTab>());
         b1 &= cont;
         b2 &= cont;
         // both entries used whole: more codes may follow (otherwise one of them held a code that does
@@ -257,6 +272,13 @@ __device__ __forceinline__ void lit12_step(Lit12& L, const uint32_t* __restrict_
 // output position stays in the region; a lookup holding no code has >= 29 - 12 > 12 bits left, so it
 // always takes the leading-ones branch (whose symbol overwrites the garbage)
 constexpr uint32_t kBodyMin = HPK_BODY_MIN;
+// The same for a table of b index bits is 2 b + 5 (12 bits: the 29 above; 13 bits: 31). A step then consumes
+// <= 2 b <= 26 bits, so it still crosses at most one dword and leaves >= 5 bits, and a lookup holding no code
+// has >= b + 5 > b bits left (13 bits: >= 18 > 13).
+template <int kTab>
+constexpr uint32_t body_min() {
+    return lut_bits<kTab>() == (uint32_t)HPK_LUT_BITS ? kBodyMin : 2u * lut_bits<kTab>() + 5u;
+}
 
 // kDup (diagnostic builds, LDS bank-conflict attribution): one access class of the step issued twice,
 // the extra access a volatile one through an LDS-qualified pointer (a volatile access through a generic
@@ -272,16 +294,16 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
     const uint32_t d3 = win32[(L.X >> 5) + 2];
     if (kDup == 2) asm volatile("" ::"v"(((const volatile HPK_LDS_AS uint32_t*)win32)[(L.X >> 5) + 2]));
     const uint32_t w = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
-    const uint32_t e1 = lut[w >> (32 - HPK_LUT_BITS)];
-    const uint32_t u1 = kTab == 3 ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
-    const uint32_t e2 = lut[(w << u1) >> (32 - HPK_LUT_BITS)];
+    const uint32_t e1 = lut[w >> (32 - lut_bits<kTab>())];
+    const uint32_t u1 = lut_l3<kTab>() ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
+    const uint32_t e2 = lut[(w << u1) >> (32 - lut_bits<kTab>())];
     if (kDup == 1) {
         const volatile HPK_LDS_AS uint32_t* vl = (const volatile HPK_LDS_AS uint32_t*)lut;
-        asm volatile("" ::"v"(vl[w >> (32 - HPK_LUT_BITS)]));
-        asm volatile("" ::"v"(vl[(w << u1) >> (32 - HPK_LUT_BITS)]));
+        asm volatile("" ::"v"(vl[w >> (32 - lut_bits<kTab>())]));
+        asm volatile("" ::"v"(vl[(w << u1) >> (32 - lut_bits<kTab>())]));
     }
-    const uint32_t u2 = kTab == 3 ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
-    const uint32_t o1 = L.o + (kTab == 3 ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1));
+    const uint32_t u2 = lut_l3<kTab>() ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
+    const uint32_t o1 = L.o + (lut_l3<kTab>() ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1));
     if (kStore != kNoStore) {
         if (kDup == 3) {
             volatile HPK_LDS_AS uint8_t* v8 = (volatile HPK_LDS_AS uint8_t*)out8;
@@ -295,21 +317,22 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
         out8[o1] = (uint8_t)e2;
         (out8 + 1)[o1] = (uint8_t)lut_sym1<kTab>(e2);
     }
-    L.o = o1 + (kTab == 3 ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2));
+    L.o = o1 + (lut_l3<kTab>() ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2));
     const uint32_t xn = L.X + u1 + u2;
     const bool cross = (xn ^ L.X) > 31u;
     L.d0 = cross ? L.d1 : L.d0;
     L.d1 = cross ? L.d2 : L.d1;
     L.d2 = cross ? d3 : L.d2;
     L.X = xn;
-    if (u2 == 0u) {  // e2 holds no code (nor e1, if u1 == 0): a 13..30-bit code or EOS at X; > 12 bits are
-                     // left (>= kBodyMin - 12 before this lookup), so the leading-ones branch of lit12_step applies
+    if (u2 == 0u) {  // e2 holds no code (nor e1, if u1 == 0): a code longer than the table's index or EOS at X;
+                     // more bits than the index are left (>= body_min - index bits before this lookup), so the
+                     // leading-ones branch of lit12_step applies
         const uint32_t wp = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
         uint32_t sy, len;
         bool eos;
         lo_decode(wp, lo, sy, len, eos);
         const uint32_t r = L.Eb - L.X;
-        if (len > r) {  // nothing fits in the > 12 bits left: huffman.rs:128-134
+        if (len > r) {  // nothing fits in the > 12 (13) bits left: huffman.rs:128-134
             L.st = HPK_PADDING_TOO_LARGE;
             L.Eb = L.X;
         } else if (eos) {  // huffman.rs:112-116
@@ -322,7 +345,7 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
             lit12_load(L, win32);
         }
     }
-    body = L.Eb - L.X >= kBodyMin;
+    body = L.Eb - L.X >= body_min<kTab>();
 }
 
 // Masked tail (decode v38): the last bits of a literal, rem = Eb - X <= 28 of them (0: an empty slot, or
@@ -344,6 +367,11 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
 //     store again. Otherwise no code fits in the r <= 12 bits left (a <= 12-bit code inside them would
 //     have been found), and the walk has ended: X moves there, st is the residual bits' status unless
 //     the body set one, and Eb = X (as after a status in the body: lit12_status then returns st).
+// With the 13-bit table (kTab 4, decode v39) a tail holds <= 30 bits (body_min is 31), still one register. An
+// entry then holds a single code only when that code and the next one take >= 14 bits together (an entry with
+// two codes holds >= 10), so two lookups that both hold a code consume >= 14 bits, four >= 28, and no code fits
+// in the <= 2 bits then left: four lookups still suffice. A lane is slow at r >= 14 (a 14..30-bit code may start
+// there and fit); in r <= 13 bits a code would have been found.
 // The state lives inverted (n = ~bits: zeros past the end), so a shift by `held` fills with ones also
 // when held is 0 (v_alignbit_b32 by 32 - held would return the fill word). ~14 VALU, one table read and
 // two byte stores per lookup, against the ~48 / 2 / 4 of a checked step, of which a tail took two.
@@ -364,10 +392,10 @@ __device__ __forceinline__ void tail12_begin(Tail12& T, const Lit12& L) {
 template <int kStore, int kTab>
 __device__ __forceinline__ void tail12_look(Tail12& T, const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8,
                                             uint32_t dmy) {
-    const uint32_t e = lut[(T.n >> (32 - HPK_LUT_BITS)) ^ (HPK_LUT_SIZE - 1u)];
-    const uint32_t held = kTab == 3 ? HPK_L3_HELD(e) : HPK_L2_HELD(e);
+    const uint32_t e = lut[(T.n >> (32 - lut_bits<kTab>())) ^ ((1u << lut_bits<kTab>()) - 1u)];
+    const uint32_t held = lut_l3<kTab>() ? HPK_L3_HELD(e) : HPK_L2_HELD(e);
     T.used += held;
-    const uint32_t codes = T.used <= T.rem ? (kTab == 3 ? HPK_L3_CODES(e) : HPK_L2_CODES(e)) : 0u;
+    const uint32_t codes = T.used <= T.rem ? (lut_l3<kTab>() ? HPK_L3_CODES(e) : HPK_L2_CODES(e)) : 0u;
     if (kStore != kNoStore) {
         out8[codes >= 1u ? T.o : dmy] = (uint8_t)e;
         (out8 + 1)[codes >= 2u ? T.o : dmy - 1u] = (uint8_t)lut_sym1<kTab>(e);
@@ -377,9 +405,10 @@ __device__ __forceinline__ void tail12_look(Tail12& T, const uint32_t* __restric
 }
 
 // returns whether the lane is slow (L is then unchanged)
+template <int kTab = 2>
 __device__ __forceinline__ bool tail12_end(const Tail12& T, Lit12& L) {
     const uint32_t r = T.rem - T.used;
-    const bool slow = r > (uint32_t)HPK_LUT_BITS;
+    const bool slow = r > lut_bits<kTab>();
     const uint32_t st = r == 0u ? HPK_OK : (r > 7u ? HPK_PADDING_TOO_LARGE : (T.n != 0u ? HPK_INVALID_PADDING : HPK_OK));
     L.X = slow ? L.X : L.X + T.used;
     L.o = slow ? L.o : T.o;
@@ -395,7 +424,7 @@ __device__ __forceinline__ bool lit12_tail(Lit12& L, const uint32_t* __restrict_
     tail12_begin(T, L);
 #pragma unroll
     for (int i = 0; i < 4; ++i) tail12_look<kStore, kTab>(T, lut, out8, dmy);
-    return tail12_end(T, L);
+    return tail12_end<kTab>(T, L);
 }
 
 // Final status of a literal whose walk has stopped; a status set by the walk wins.
