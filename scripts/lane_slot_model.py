@@ -29,7 +29,9 @@ import hpack_ref  # noqa: E402
 
 LUT_BITS = 12  # --lut-bits: the two-symbol table's index bits (the v38 kernel's 12; 13 since v39)
 BODY_MIN = 29  # 2 * LUT_BITS + 5
-IMG = 5888 - 256  # --image: usable image bytes per wave (v38: kWaveImg less the dummy slots; v39: 5040, all of kWaveImg)
+IMG = 5888 - 256  # --image: usable image bytes per wave (v38: kWaveImg less the dummy slots; v39 and v40: 5040, all
+                  # of kWaveImg. With --window 3008 the window cuts config-2 fills, not the image: 4784 gives the same
+                  # 108.3 literals per fill as 5040, 4528 gives 102.6)
 
 
 def build_lut():

@@ -2,7 +2,10 @@
 """Per-wave phase stamps of the v25 wave-fill decode kernel (diagnostic build, HPK_DEBUG_MODE=3,
 HPK_DECODE_KERNEL=wave): `python scripts/wave_stamps.py [config5|c2_4m|config2]`. One JSON line: mean
 cycles per wave in each phase and its share of the wave's total, the lane loop split into its body rounds
-and its tails, and the per-fill figures (cycles, rounds, fills per wave)."""
+and its tails, and the per-fill figures (cycles, rounds, fills per wave). Since decode v40 "queue" holds the
+queue reads ("prefetch_issue_qread" the prefetch issue and the first literal's load only), and "write_back" the
+issue of the image's read-out before the sort plus the stores after it; a stamp waits for every LDS
+operation in flight, so the stamped build does not run the sort under the read-out as the product does."""
 import ctypes
 import json
 import os
