@@ -8,7 +8,12 @@
 //   1 the same without the stores (kNoStore)
 //   2 the bare chain: window dword, two lookups, the bit position and the pair slide (no output)
 //   3 two literals per lane stepped alternately (product step on each: two independent chains)
-// at 1, 4 and 16 waves per CU (one workgroup). One JSON line per (variant, waves).
+//   4 the lane loop's round of decode v40: four product steps, each under its own `if (body)`, the wave's
+//     `any` once a round
+//   5 / 6 / 7 the round of nested steps (lit12_round, decode v41), four steps: long codes inline / a parked
+//     lane out of the round / a parked lane in it
+// at 1, 4 and 16 waves per CU (one workgroup). One JSON line per (variant, waves). The round variants walk the
+// same literals, so their steps are those of variant 0 (counted by an untimed second walk).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,8 +62,20 @@ __global__ __launch_bounds__(1024) void probe(const uint32_t* __restrict__ lut3,
     make(L, 0);
     make(N, 1);
     uint32_t steps = 0, sink = 0;
+    const Lit12 L0 = L;
     const uint64_t t0 = __builtin_amdgcn_s_memtime();
-    if (kVar == 3) {
+    if (kVar >= 4) {
+        bool body = L.Eb - L.X >= kBodyMin;
+        while (__any(body)) {
+            if (kVar == 4) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (body) lit12_body<kPred, 3>(L, s_win, s_lut, s_lo, s_img, body);
+            } else {
+                lit12_round<kPred, 3, 4, kVar - 5>(L, s_win, s_lut, s_lo, s_img, body, [](bool p) { return __any(p) != 0; });
+            }
+        }
+    } else if (kVar == 3) {
         bool bl = L.Eb - L.X >= kBodyMin, bn = N.Eb - N.X >= kBodyMin;
         while (__any(bl | bn)) {
             if (bl) lit12_body<kPred, 3>(L, s_win, s_lut, s_lo, s_img, bl);
@@ -91,6 +108,15 @@ __global__ __launch_bounds__(1024) void probe(const uint32_t* __restrict__ lut3,
         }
     }
     const uint64_t t1 = __builtin_amdgcn_s_memtime();
+    if (kVar >= 4) {  // the steps, as variant 0 counts them
+        sink += L.X;
+        L = L0;
+        bool body = L.Eb - L.X >= kBodyMin;
+        while (__any(body)) {
+            if (body) lit12_body<kPred, 3>(L, s_win, s_lut, s_lo, s_img, body);
+            steps += body ? 1u : 0u;
+        }
+    }
     // the wave's slowest lane: its steps
     uint32_t ms = steps;
     for (int d = 32; d >= 1; d >>= 1) ms = max(ms, (uint32_t)__shfl_xor((int)ms, d));
@@ -145,6 +171,10 @@ int main() {
                 case 0: hipLaunchKernelGGL(probe<0>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
                 case 1: hipLaunchKernelGGL(probe<1>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
                 case 2: hipLaunchKernelGGL(probe<2>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
+                case 4: hipLaunchKernelGGL(probe<4>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
+                case 5: hipLaunchKernelGGL(probe<5>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
+                case 6: hipLaunchKernelGGL(probe<6>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
+                case 7: hipLaunchKernelGGL(probe<7>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
                 default: hipLaunchKernelGGL(probe<3>, dim3(1), dim3(64 * waves), 0, 0, d_lut, d_lo, d_win, d_nb, d_out); break;
             }
             CK(hipGetLastError());
@@ -159,7 +189,7 @@ int main() {
         printf("{\"variant\": %d, \"waves\": %d, \"cycles_per_wave\": %.0f, \"steps\": %.1f, \"cycles_per_step\": %.1f}\n",
                var, waves, cyc / waves, st / waves, cyc / st);
     };
-    for (int var = 0; var < 4; ++var)
+    for (int var = 0; var < 8; ++var)
         for (int waves : {1, 4, 16}) run(var, waves);
     return 0;
 }

@@ -288,9 +288,11 @@ constexpr uint32_t body_min() {
 #ifndef HPK_LDS_AS
 #define HPK_LDS_AS __attribute__((address_space(3)))
 #endif
+// lit12_body's first part: the two lookups, their stores and the advance; returns u2, the bits the second
+// entry holds (0: a code longer than the table's index, or EOS, starts at the new X; lit12_body_long)
 template <int kStore, int kTab = 2, int kDup = 0>
-__device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict__ win32, const uint32_t* __restrict__ lut,
-                                           const uint16_t* __restrict__ lo, uint8_t* __restrict__ out8, bool& body) {
+__device__ __forceinline__ uint32_t lit12_body_main(Lit12& L, const uint32_t* __restrict__ win32,
+                                                    const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8) {
     const uint32_t d3 = win32[(L.X >> 5) + 2];
     if (kDup == 2) asm volatile("" ::"v"(((const volatile HPK_LDS_AS uint32_t*)win32)[(L.X >> 5) + 2]));
     const uint32_t w = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
@@ -324,25 +326,84 @@ __device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict_
     L.d1 = cross ? L.d2 : L.d1;
     L.d2 = cross ? d3 : L.d2;
     L.X = xn;
-    if (u2 == 0u) {  // e2 holds no code (nor e1, if u1 == 0): a code longer than the table's index or EOS at X;
-                     // more bits than the index are left (>= body_min - index bits before this lookup), so the
-                     // leading-ones branch of lit12_step applies
-        const uint32_t wp = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
-        uint32_t sy, len;
-        bool eos;
-        lo_decode(wp, lo, sy, len, eos);
-        const uint32_t r = L.Eb - L.X;
-        if (len > r) {  // nothing fits in the > 12 (13) bits left: huffman.rs:128-134
-            L.st = HPK_PADDING_TOO_LARGE;
-            L.Eb = L.X;
-        } else if (eos) {  // huffman.rs:112-116
-            L.st = HPK_EOS_IN_STRING;
-            L.Eb = L.X;
-        } else {
-            if (kStore != kNoStore) out8[L.o] = (uint8_t)sy;
-            L.o += 1;
-            L.X += len;
-            lit12_load(L, win32);
+    return u2;
+}
+
+// lit12_body's second part, after a second lookup that held no code (nor the first, if u1 == 0): a code longer
+// than the table's index or EOS at X; more bits than the index are left (>= body_min - index bits before that
+// lookup), so the leading-ones branch of lit12_step applies
+template <int kStore>
+__device__ __forceinline__ void lit12_body_long(Lit12& L, const uint32_t* __restrict__ win32, const uint16_t* __restrict__ lo,
+                                                uint8_t* __restrict__ out8) {
+    const uint32_t wp = __builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X);
+    uint32_t sy, len;
+    bool eos;
+    lo_decode(wp, lo, sy, len, eos);
+    const uint32_t r = L.Eb - L.X;
+    if (len > r) {  // nothing fits in the > 12 (13) bits left: huffman.rs:128-134
+        L.st = HPK_PADDING_TOO_LARGE;
+        L.Eb = L.X;
+    } else if (eos) {  // huffman.rs:112-116
+        L.st = HPK_EOS_IN_STRING;
+        L.Eb = L.X;
+    } else {
+        if (kStore != kNoStore) out8[L.o] = (uint8_t)sy;
+        L.o += 1;
+        L.X += len;
+        lit12_load(L, win32);
+    }
+}
+
+template <int kStore, int kTab = 2, int kDup = 0>
+__device__ __forceinline__ void lit12_body(Lit12& L, const uint32_t* __restrict__ win32, const uint32_t* __restrict__ lut,
+                                           const uint16_t* __restrict__ lo, uint8_t* __restrict__ out8, bool& body) {
+    if (lit12_body_main<kStore, kTab, kDup>(L, win32, lut, out8) == 0u) lit12_body_long<kStore>(L, win32, lo, out8);
+    body = L.Eb - L.X >= body_min<kTab>();
+}
+
+// A round of kSteps body steps (decode v41, the wave kernel's lane loop). The steps are NESTED: step s + 1 lives
+// inside step s's `if (body)`. Within a round `body` only goes from true to false, so the active lanes only
+// narrow and every step's region ends at the one join behind the round: a step costs one compare and one
+// narrowing of exec, and no value of the walk is live out of a step in a second register. kDefer says what a
+// step does with a second lookup that holds no code (a 13..30-bit code or EOS at the new X):
+//   0  the leading-ones block inline, as lit12_body does;
+//   1  the lane is parked: it has advanced by u1 + u2 and stored its (harmless) bytes, and drops out of the rest
+//      of the round like a lane whose body ended;
+//   2  the lane is parked and stays in the round while >= body_min bits are left: a body step at a position
+//      where no code of <= index bits starts holds u1 = u2 = 0, so it moves nothing and stores the two garbage
+//      bytes at o and o + 1 that the step before it (or lit12_body's u1 == 0 case) stores there anyway; the
+//      lane is parked exactly when its last executed step's second lookup held no code.
+// Behind a deferred round ONE test, wave-wide by the caller's `any` (the CPU replay: the lane's own flag), runs
+// the leading-ones block for the parked lanes and recomputes their `body`: a parked lane's next action is the
+// lookup lit12_body would have done, from the same state, so the results are the same byte for byte and only the
+// slot in which it happens moves (a parked lane loses at most kSteps - 1 step slots).
+template <int kStore, int kTab, int kDefer, int kDup, int kLeft>
+__device__ __forceinline__ void lit12_round_steps(Lit12& L, const uint32_t* __restrict__ win32,
+                                                  const uint32_t* __restrict__ lut, const uint16_t* __restrict__ lo,
+                                                  uint8_t* __restrict__ out8, bool go, uint32_t& u2) {
+    if (go) {
+        u2 = lit12_body_main<kStore, kTab, kDup>(L, win32, lut, out8);
+        if (kDefer == 0 && u2 == 0u) lit12_body_long<kStore>(L, win32, lo, out8);
+        if constexpr (kLeft > 1) {
+            go = L.Eb - L.X >= body_min<kTab>();
+            if (kDefer == 1) go &= u2 != 0u;
+            lit12_round_steps<kStore, kTab, kDefer, kDup, kLeft - 1>(L, win32, lut, lo, out8, go, u2);
+        }
+    }
+}
+
+// `body` is, before and after the round, whether the lane's next step may be a body step: L.Eb - L.X >= body_min
+// (made from the state behind the round, so that no flag is carried through the steps)
+template <int kStore, int kTab, int kSteps, int kDefer, int kDup = 0, class Any>
+__device__ __forceinline__ void lit12_round(Lit12& L, const uint32_t* __restrict__ win32, const uint32_t* __restrict__ lut,
+                                            const uint16_t* __restrict__ lo, uint8_t* __restrict__ out8, bool& body,
+                                            Any any) {
+    uint32_t u2 = 1u;  // the second lookup's bits held, of the lane's last executed step (no step: not parked)
+    lit12_round_steps<kStore, kTab, kDefer, kDup, kSteps>(L, win32, lut, lo, out8, body, u2);
+    if (kDefer != 0) {
+        const bool parked = u2 == 0u;
+        if (any(parked)) {
+            if (parked) lit12_body_long<kStore>(L, win32, lo, out8);
         }
     }
     body = L.Eb - L.X >= body_min<kTab>();

@@ -45,6 +45,11 @@
 #define HPK_BODY_UNROLL 4  // body steps between the checks for a lane whose literal's body ended (2: config 5 +2.5 %;
                            // v39, ~19.5 executed steps per fill: 3 678.5-699.9 against 681.7-691.0 us, within the spread)
 #endif
+#ifndef HPK_BODY_ROUND
+#define HPK_BODY_ROUND 3  // the lane loop's round of HPK_BODY_UNROLL body steps (v41): 0 = a step at a time, each under its
+                          // own `if (body)` (v40); 1 = nested steps (lit12_round, hpk_walk.h), long codes inline; 2 / 3 =
+                          // nested, long codes once a round (a parked lane drops out / stays in the round)
+#endif
 #ifndef HPK_WAVE_TAB
 #define HPK_WAVE_TAB 4  // the wave kernel's two-symbol table (lut_bits, hpk_walk.h): 4 = the LUT3 layout (byte-wide
                         // "bits held", v28) at 13 index bits (v39); 3 = the same at 12 bits, 2 = LUT2
@@ -865,13 +870,17 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 // tail, the checked steps of v27 only for its slow lanes). A lane's first literal waits between the
                 // two phases as (aX, aO, aSt). (Measured and not taken, round 5: accumulated dword
                 // stores, dword ORs, both bodies or both tails in one block)
+                constexpr bool kRound = HPK_BODY_ROUND != 0 && kMode != 6;  // (mode 6 adds its VALU to the v40 steps)
                 bool body = L.Eb - L.X >= body_min<kTab>();
                 uint32_t aX = L.X, aO = L.o, aSt = L.st;
                 bool aAct = L.act, onA = true;
                 for (;;) {
                     dg_add(9, 1u);
+                    if (kRound)  // v41: the round's steps nested, one narrowing of exec each (lit12_round)
+                        lit12_round<kStore, kTab, HPK_BODY_UNROLL, HPK_BODY_ROUND - 1, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(
+                            L, wl32, s_lut, s_lo, ol8, body, [](bool p) { return __any(p) != 0; });
 #pragma unroll
-                    for (int s = 0; s < HPK_BODY_UNROLL; ++s) {
+                    for (int s = 0; !kRound && s < HPK_BODY_UNROLL; ++s) {
                         if (body)
                             lit12_body<kStore, kTab, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(L, wl32, s_lut, s_lo, ol8,
                                                                                                    body);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CPU model of the wave-fill kernel's lane loop (hpk_wave.h, step 7), for judging scheduling variants
 without a GPU: `python scripts/lane_slot_model.py [--n 200000] [--window 3072] [--image 5632] [--lut-bits 12]
-[--unroll 4] [--key bytes2]`.
+[--unroll 4] [--key bytes2] [--defer-park out|in]`.
 
 It draws config-2-distribution literals (decoded length U[8,64], loona_amd/data/char_model.json), encodes
 them with the RFC 7541 code (lengths from oracle/hpack_ref.py), cuts the batch into fills as the kernel does
@@ -15,6 +15,10 @@ the masked tail (lit12_tail: whether a lane falls back). One JSON line, per fill
   literals, body rounds (loop iterations of --unroll step slots), step slots, executed steps (slots in
   which some lane stepped), useful steps (lane steps / 64), max-pair steps (the lane with the most body
   steps: the bound no schedule beats), checked-tail iterations, fills with a slow masked tail.
+--defer-park models the round of nested steps with long codes taken once a round (lit12_round, decode v41): a
+lane whose step's second lookup holds no code is parked until the round's end, out of the round's remaining step
+slots (`out`) or repeating a step that moves nothing while >= body-min bits are left (`in`, the kernel's choice:
+such a slot counts as executed); the line then also holds the parked lane-steps and the slots they lost per fill.
 numpy only; it does not load the GPU library."""
 import argparse
 import json
@@ -120,6 +124,7 @@ def walk(stream, lut, p0, nbytes):
     E = X + nbytes * 8
     body = np.zeros(n, np.int64)
     ended = np.zeros(n, bool)  # a status in the body: no tail
+    parks = {}  # literal -> {body step (0-based) whose second lookup held no code: >= BODY_MIN bits left there}
 
     def park(i):  # the leading-ones branch for literal i at X[i]: returns whether the walk goes on
         ln, eos = long_code_len(stream.w30(X[i]))
@@ -137,6 +142,7 @@ def walk(stream, lut, p0, nbytes):
         X[act] += u1 + u2
         body[act] += 1
         for i in act[u2 == 0]:
+            parks.setdefault(int(i), {})[int(body[i]) - 1] = bool(E[i] - X[i] >= BODY_MIN)
             if not park(i):
                 ended[i] = True
         act = act[(E[act] - X[act] >= BODY_MIN)]
@@ -181,7 +187,7 @@ def walk(stream, lut, p0, nbytes):
             if not park(act[j]):
                 go[j] = False
         act = act[go]
-    return body, tail, slow
+    return body, tail, slow, parks
 
 
 def main():
@@ -198,6 +204,8 @@ def main():
                     help="longest-first sort key: 32 classes of 2 encoded bytes (the kernel's), 16 of 4, the body "
                          "steps themselves (an oracle), or arrival order")
     ap.add_argument("--chunk", type=int, default=3900, help="literals per chunk claim (a fill ends at its chunk's end)")
+    ap.add_argument("--defer-park", choices=["out", "in"], default=None,
+                    help="long codes once a round: a parked lane leaves the round's remaining slots / stays in them")
     a = ap.parse_args()
     defaults = (a.lut_bits, a.image) == (LUT_BITS, IMG)
     LUT_BITS, BODY_MIN, IMG = a.lut_bits, 2 * a.lut_bits + 5, a.image
@@ -206,9 +214,9 @@ def main():
     nbytes = np.diff(off)
     ooff = np.zeros(a.n + 1, np.int64)
     np.cumsum(nbytes * 8 // 5, out=ooff[1:])
-    body, tail, slow = walk(Stream(blob), build_lut(), off[:-1].copy(), nbytes)
+    body, tail, slow, parks = walk(Stream(blob), build_lut(), off[:-1].copy(), nbytes)
 
-    fills = rounds = executed = lits = 0
+    fills = rounds = executed = lits = parked = lost = 0
     useful = maxpair = tail_it = slow_fills = 0.0
     cur = 0
     while cur < a.n:
@@ -228,12 +236,27 @@ def main():
         q = np.zeros(128, np.int64)
         q[:k] = body[idx]
         A, B = q[:64].copy(), q[127:63:-1].copy()  # lane i: slots i and 127 - i
+        qi = np.full(128, -1, np.int64)
+        qi[:k] = idx
+        LA, LB = qi[:64].copy(), qi[127:63:-1].copy()  # the lanes' literals
         curb, on_a = A.copy(), np.ones(64, bool)
         while True:
             rounds += 1
+            stall = np.zeros(64, bool)  # (--defer-park) parked in this round
+            stay = np.zeros(64, bool)   # ... and still stepping (in place)
             for _ in range(a.unroll):
-                m = curb > 0
-                executed += bool(m.any())
+                m = (curb > 0) & ~stall
+                executed += bool(m.any() or stay.any())
+                lost += int((stall & (curb > 0)).sum())
+                if a.defer_park:
+                    for ln in np.nonzero(m)[0]:
+                        lit = int(LA[ln] if on_a[ln] else LB[ln])
+                        if lit in parks:
+                            step = int((A[ln] if on_a[ln] else B[ln]) - curb[ln])
+                            if step in parks[lit]:
+                                stall[ln] = True
+                                stay[ln] = a.defer_park == "in" and parks[lit][step]
+                                parked += 1
                 curb -= m
             done = curb == 0
             if done.any():
@@ -251,6 +274,9 @@ def main():
         cur += k
     f = float(fills)
     extra = {} if defaults else {"lut_bits": LUT_BITS, "body_min": BODY_MIN, "image": IMG}
+    if a.defer_park:
+        extra.update({"defer_park": a.defer_park, "parked_lane_steps_per_fill": round(parked / f, 3),
+                      "lane_slots_lost_per_fill": round(lost / f, 3)})
     print(json.dumps({
         **extra, "literals": a.n, "window": a.window, "unroll": a.unroll, "key": a.key, "chunk": a.chunk, "fills": fills,
         "literals_per_fill": round(lits / f, 1), "body_rounds_per_fill": round(rounds / f, 2),
