@@ -401,6 +401,11 @@ int hpk_test_bound_scan(hpk_ctx* ctx, const uint32_t* in_off, uint32_t n, uint32
  * 16-byte boundaries of the destination address) and how many literals' offsets a workgroup stages in
  * LDS at a time. The tests place their edge cases relative to these. */
 int hpk_test_pack_geometry(uint32_t* tile_bytes, uint32_t* lds_literals);
+/* Testing only: the encode kernel's geometry: input bytes per tile, bytes of the LDS output image,
+ * literals per tile, input bytes per thread, and the literal count up to which a batch runs in one
+ * workgroup. The tests place their edge cases relative to these. */
+int hpk_test_encode_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32_t* tile_literals,
+                             uint32_t* thread_bytes, uint32_t* one_wg_literals);
 /* Testing only: how many decode calls of this context the small-call mode's persistent kernel has
  * answered (hpk_ctx_set_small_mode), so the tests can tell it ran. */
 uint64_t hpk_test_small_calls(const hpk_ctx* ctx);

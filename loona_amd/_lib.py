@@ -84,6 +84,7 @@ EXPORTS = (
     "hpk_test_fail_batches",
     "hpk_test_bound_scan",
     "hpk_test_pack_geometry",
+    "hpk_test_encode_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
     "hpk_ctx_set_decode_kernel",
@@ -261,6 +262,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_pack_geometry"):
             L.hpk_test_pack_geometry.argtypes = [c_u32p, c_u32p]
             L.hpk_test_pack_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_encode_geometry"):
+            L.hpk_test_encode_geometry.argtypes = [c_u32p] * 5
+            L.hpk_test_encode_geometry.restype = ctypes.c_int
         L.hpk_version.argtypes = []
         L.hpk_version.restype = ctypes.c_char_p
         _lib = L

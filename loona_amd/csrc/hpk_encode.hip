@@ -112,6 +112,13 @@ __global__ __launch_bounds__(ENC_BLOCK) void hpk_encode_kernel(EncodeArgs a) {
 // (30 dwords), started at dword (tid & 31) so the lanes of a wave do not all hit one address.
 constexpr int kEPh = 64;
 
+// The product geometry (hpk_launch_encode's launch and hpk_test_encode_geometry's answer): threads per
+// workgroup, bytes of the LDS output image, literals per tile, input bytes per thread; and the literals
+// a workgroup is given at least (the grid is ceil(n / kProdPerWg) workgroups until the CUs are full, so
+// a batch of at most kProdPerWg literals runs in one workgroup).
+constexpr int kProdEB = 512, kProdEO = 56 * 1024, kProdEQ = 1024, kProdEBytes = 32;
+constexpr uint32_t kProdPerWg = 64;
+
 template <int kEB, int kEO, int kEQ, int kP = 0>
 struct EncLds {
     uint32_t img[kEO / 4 + kEPh];  // the tile's output span, big-endian dwords; then the phantom dwords
@@ -126,7 +133,8 @@ struct EncLds {
     uint32_t slast[kEB + 1];     // 1 + the last (non-empty) literal starting in word h's bytes, 0 if none
     uint32_t live[(kEO / 16 + 31) / 32];  // image chunks holding output bytes (the rest is slack)
     uint32_t ctr[4];             // [0] literals in the tile, [1] bad offsets seen, [2] a literal of the tile
-                                 // has less room than 30 bits per input byte (pass 2 takes the checked path)
+                                 // has less room than 30 bits per input byte (pass 2 takes the checked path),
+                                 // [3] the window's first literal with bad offsets (written only once [1] is set)
     uint32_t split[2 * hpksplit::kMaxRounds];  // split_by_bytes's counters
     unsigned long long prof[kP ? kEB / 64 : 1][12];  // diagnostic build (kProf): per-wave phase cycles
 };
@@ -245,6 +253,7 @@ __global__ __launch_bounds__(kEB, 4) void hpk_encode2(EncodeArgs a) {
     };
     uint32_t cur = BA;
     uint32_t gin = 0, gout = 0;  // the tile's input / output start (base-relative: + mis)
+    const uint32_t range_end = BB;  // (BB is pulled in to the range's first literal with bad offsets, once seen)
     if (cur < BB) {
         gin = a.in_off[cur] + a.in_mis;
         gout = a.out_off[cur] + a.out_mis;
@@ -299,13 +308,31 @@ __global__ __launch_bounds__(kEB, 4) void hpk_encode2(EncodeArgs a) {
         EPROF(1);
         lds_barrier_e();
         EPROF(11);
-        if (S.ctr[1]) {  // bad offsets (block-uniform): the range's remaining literals are void
-            for (uint32_t i = cur + tid; i < BB; i += kEB) {
-                a.out_len[i] = 0;
-                a.status[i] = (uint8_t)HPK_BAD_OFFSETS;
+        if (S.ctr[1]) {  // bad offsets (block-uniform): the range's literals from the first bad one on are void
+            // the window's first bad literal (ctr[3]) becomes the range's end: the literals before it have
+            // good offsets and are encoded first, the rest is voided after the loop (rare path: its
+            // barriers and the second fill do not matter)
+            if (tid == 0) S.ctr[3] = cntl;
+            lds_barrier_e();
+#pragma unroll
+            for (int r = 0; r < kEMeta; ++r) {
+                const uint32_t t = tid + (uint32_t)kEB * r;
+                if (t < cntl && !(pi0[r] <= pi1[r] && pi1[r] <= a.in_cap && po0[r] <= po1[r] && po1[r] <= a.out_cap))
+                    atomicMin(&S.ctr[3], t);
             }
-            if (tid == 0) *a.err = 1u;
-            break;
+            lds_barrier_e();
+            // (literals past the bad one may have marked the start map: clear what the fill wrote)
+            if (tid == 0) {  // (ctr[1] was read before this branch's barriers)
+                S.ctr[0] = 0;
+                S.ctr[1] = 0;
+                S.ctr[2] = 0;
+            }
+            for (uint32_t w = tid; w <= (uint32_t)kEB; w += kEB) {
+                S.smap[w] = 0;
+                S.slast[w] = 0;
+            }
+            BB = cur + S.ctr[3];
+            continue;  // (the bad literal is the window's first: the loop ends)
         }
         EPROF(1);
         const uint32_t k = S.ctr[0];
@@ -504,8 +531,11 @@ __global__ __launch_bounds__(kEB, 4) void hpk_encode2(EncodeArgs a) {
             uint32_t dq = (ob + bp) >> 5, n = (ob + bp) & 31u;
             uint64_t acc = 0;
             bool first = true;
+            // (acc != 0 only with n > 0 and bits accepted at bp <= cap, so dq lies in the literal's region:
+            // a thread that starts past its literal's capacity, where (ob + bp) >> 5 can pass the image,
+            // holds no bits and touches nothing)
             auto flush_run = [&]() {
-                if (n) atomicOr(&S.img[dq], (uint32_t)(acc << (32u - n)));
+                if (acc) atomicOr(&S.img[dq], (uint32_t)(acc << (32u - n)));
                 n = 0;
                 acc = 0;
             };
@@ -606,8 +636,10 @@ __global__ __launch_bounds__(kEB, 4) void hpk_encode2(EncodeArgs a) {
                 }
             }
             if (tid < 32) {  // the partial chunks at the two ends, one byte per lane
-                const uint32_t g = tid < 16 ? 0u : (c1 - 1u) << 4;
-                const bool partial = !(g >= G0 && g + 16u <= G1) && (tid < 16 || c1 - 1u != 0u);
+                // (lanes 16-31: the last chunk when it is not also the first; c1 == 0, a span of no bytes
+                // at an aligned start, has neither)
+                const uint32_t g = tid < 16 || c1 < 2u ? 0u : (c1 - 1u) << 4;
+                const bool partial = !(g >= G0 && g + 16u <= G1) && (tid < 16 ? c1 != 0u : c1 > 1u);
                 const uint32_t x = g + (tid & 15u);
                 if (partial && x >= G0 && x < G1) {
                     const uint32_t w = S.img[x >> 2];
@@ -621,6 +653,13 @@ __global__ __launch_bounds__(kEB, 4) void hpk_encode2(EncodeArgs a) {
         cur = cur_n;
         gin = gin_n;
         gout = gout_n;
+    }
+    if (BB < range_end) {  // from the range's first literal with bad offsets on
+        for (uint32_t i = BB + tid; i < range_end; i += kEB) {
+            a.out_len[i] = 0;
+            a.status[i] = (uint8_t)HPK_BAD_OFFSETS;
+        }
+        if (tid == 0) *a.err = 1u;
     }
     if (kProf) {
         __syncthreads();
@@ -669,7 +708,7 @@ int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b) {
 #endif
     // per = workgroups per CU; fewer when the batch is small (>= ~64 literals per workgroup)
     const int per = cfg == 1 ? 1 : 2;
-    uint64_t blocks = ((uint64_t)b.n + 63) / 64;
+    uint64_t blocks = ((uint64_t)b.n + kProdPerWg - 1u) / kProdPerWg;
     // (the small-call mode's persistent workgroups hold sm_wgs CUs, hpk_persist.h: left out of the grid)
     const uint64_t cus = (uint64_t)c->num_cu - (c->sm_launched && c->sm_max ? (uint64_t)c->sm_wgs : 0u);
     if (blocks > cus * per) blocks = cus * per;
@@ -684,13 +723,26 @@ int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b) {
             if (!g_eprof) HIP_TRY(hipMalloc(&g_eprof, 16 * sizeof(unsigned long long)));
             HIP_TRY(hipMemsetAsync(g_eprof, 0, 16 * sizeof(unsigned long long), c->stream));
             a.prof = g_eprof;
-            hipLaunchKernelGGL((hpk_encode2<512, 56 * 1024, 1024, 32, 1>), grid, dim3(512), 0, c->stream, a);
+            hipLaunchKernelGGL((hpk_encode2<kProdEB, kProdEO, kProdEQ, kProdEBytes, 1>), grid, dim3(kProdEB), 0,
+                               c->stream, a);
             break;
 #endif
         default:  // product: two 512-thread workgroups per CU, 32 bytes per thread
-            hipLaunchKernelGGL((hpk_encode2<512, 56 * 1024, 1024, 32>), grid, dim3(512), 0, c->stream, a);
+            hipLaunchKernelGGL((hpk_encode2<kProdEB, kProdEO, kProdEQ, kProdEBytes>), grid, dim3(kProdEB), 0,
+                               c->stream, a);
     }
     HIP_TRY(hipGetLastError());
+    return HPK_E_OK;
+}
+
+extern "C" int hpk_test_encode_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32_t* tile_literals,
+                                        uint32_t* thread_bytes, uint32_t* one_wg_literals) {
+    if (!tile_bytes || !image_bytes || !tile_literals || !thread_bytes || !one_wg_literals) return HPK_E_INVAL;
+    *tile_bytes = kProdEB * kProdEBytes;
+    *image_bytes = kProdEO;
+    *tile_literals = kProdEQ;
+    *thread_bytes = kProdEBytes;
+    *one_wg_literals = kProdPerWg;
     return HPK_E_OK;
 }
 
