@@ -187,6 +187,50 @@ int hpk_encode_batch(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const 
                      uint8_t* out_blob, size_t out_cap, const uint32_t* out_off, uint32_t* out_len,
                      uint8_t* status, int flags);
 
+/* ---- batch encode: the encoded lengths alone ----------------------------------------------
+ * out_len[i] = hpk_huffman_encoded_len of literal i = in_blob[in_off[i] .. in_off[i+1]): ceil(code bits / 8),
+ * 0 for an empty literal, with no byte encoded. It is the number the H-bit branch that
+ * encode_string_literal (crates/loona-hpack/src/encoder.rs:296-307) would add needs per string: RFC 7541
+ * §5.2 is used only where this is strictly below the raw length. A literal whose offsets decrease or pass
+ * in_cap counts 0 and sets the sticky flag (a synchronous call then returns HPK_E_INVAL): hpk_pack_batch's
+ * rule; it voids no other literal. Cost of a bad batch: the up to 1,024 consecutive literals the kernel
+ * was looking at when it met the bad one are each summed by one lane, byte by byte, large ones included. Nothing outside [in_blob, in_blob + in_cap) is read (as hpk_encode_batch,
+ * in whole aligned 16-byte chunks that hold a byte of the blob). n == 0 is a no-op. Device pointers only
+ * (HPK_PTR_DEVICE, optionally HPK_ASYNC), on the context's stream; always the launch path. No scratch. */
+int hpk_encoded_len_batch(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
+                          uint32_t n, uint32_t* out_len, int flags);
+
+/* ---- batch encode, packed output: the encoded bytes end to end, in literal order ------------
+ * hpk_encode_batch needs a region per literal, and the only size known before encoding is
+ * hpk_encoded_bound (3.75x the input; header text encodes to about 0.8x). This form needs none (the H-bit
+ * branch of crates/loona-hpack/src/encoder.rs:296-307 writes each string right after its length prefix):
+ * out_off (n+1 entries) is an OUTPUT, the exclusive sum of out_len; literal i's encoding is
+ * out_blob[out_off[i] .. out_off[i+1]) with no gap, and out_off[n] is the encoded total. n == 0 writes
+ * out_off[0] = 0. The bytes are exactly hpk_encode_batch's for a region that is large enough, out_len[i] is
+ * the full encoded length, and status[i] is HPK_OK or HPK_BAD_OFFSETS, never HPK_OUTPUT_OVERFLOW. The result
+ * is hpk_decode_batch_packed's input as it stands (out_off as in_off).
+ * out_cap may be any size: the bytes below min(out_off[n], out_cap) are written, nothing at or past that
+ * point nor outside [out_blob, out_blob + out_cap), and out_off, out_len and status are complete either way.
+ * If out_off[n] > out_cap a synchronous call returns HPK_E_NOSPACE; after HPK_ASYNC the caller compares.
+ * Bad offsets: a literal whose input offsets decrease or pass in_cap gets HPK_BAD_OFFSETS and out_len 0 and
+ * sets the sticky flag (HPK_E_INVAL from the synchronous call, which wins over HPK_E_NOSPACE). The call may
+ * void other literals of the batch the same way (this version voids none: every other literal is encoded);
+ * whatever it voids, out_off is the exclusive sum of out_len and every literal with status HPK_OK holds its
+ * complete encoding. If the encoded total passes HPK_MAX_OFFSET, every out_off is 0, every literal is void
+ * (HPK_BAD_OFFSETS, out_len 0), nothing is written to out_blob and the flag is set; hpk_encoded_bound(in_cap)
+ * may pass 4 GiB as long as the true total does not.
+ * Device pointers only (HPK_PTR_DEVICE, optionally HPK_ASYNC), on the context's stream with its per-stream
+ * scratch; always the launch path. How: the length pass (hpk_encoded_len_batch's kernel) writes out_len and
+ * status, a scan of out_len with 64-bit tile sums writes out_off, and the encode kernel's packed
+ * instantiation writes every literal at its final place. The scratch is the scan's tile sums (8 bytes per
+ * 4,096 literals): there is no intermediate blob and no second copy. The input offsets must not change
+ * between the call and its completion. Cost of a bad batch: the length pass as hpk_encoded_len_batch, and
+ * in the encode every literal from the bad one to the end of its workgroup's share of the batch (the batch
+ * is split by bytes over up to two workgroups per CU) is encoded by one lane, byte by byte. */
+int hpk_encode_batch_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                            uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
+                            uint8_t* status, int flags);
+
 /* Which decode kernel a context's batches use. All give identical results (the parity tests run
  * every case through each); they differ in speed. HPK_DECODE_AUTO (the default): the wave-fill kernel
  * for every batch (since round 6; it had been the workgroup-fill kernel below 4M literals). */
@@ -406,6 +450,11 @@ int hpk_test_pack_geometry(uint32_t* tile_bytes, uint32_t* lds_literals);
  * workgroup. The tests place their edge cases relative to these. */
 int hpk_test_encode_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32_t* tile_literals,
                              uint32_t* thread_bytes, uint32_t* one_wg_literals);
+/* Testing only: the length pass's geometry (hpk_encoded_len_batch, hpk_encode_batch_packed): the input bytes
+ * of a stretch (a workgroup walks its literals in stretches that start at the 16-byte boundary at or below
+ * the first unfinished literal's start, or where the previous stretch ended when a literal passed its end),
+ * the literals it looks at per stretch, and the literal count up to which a batch runs in one workgroup. */
+int hpk_test_enclen_geometry(uint32_t* stretch_bytes, uint32_t* window_literals, uint32_t* one_wg_literals);
 /* Testing only: how many decode calls of this context the small-call mode's persistent kernel has
  * answered (hpk_ctx_set_small_mode), so the tests can tell it ran. */
 uint64_t hpk_test_small_calls(const hpk_ctx* ctx);

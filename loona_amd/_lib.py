@@ -52,6 +52,8 @@ EXPORTS = (
     "hpk_decode_batch_packed",
     "hpk_pack_batch",
     "hpk_encode_batch",
+    "hpk_encoded_len_batch",
+    "hpk_encode_batch_packed",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -85,6 +87,7 @@ EXPORTS = (
     "hpk_test_bound_scan",
     "hpk_test_pack_geometry",
     "hpk_test_encode_geometry",
+    "hpk_test_enclen_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
     "hpk_ctx_set_decode_kernel",
@@ -171,6 +174,11 @@ def lib() -> ctypes.CDLL:
         batch_fns = [L.hpk_decode_batch, L.hpk_encode_batch, L.hpk_decode_batch_compact]
         if hasattr(L, "hpk_decode_batch_packed"):  # (an A/B build of an older source has no packed form)
             batch_fns.append(L.hpk_decode_batch_packed)
+        if hasattr(L, "hpk_encode_batch_packed"):  # (likewise: no packed encode)
+            batch_fns.append(L.hpk_encode_batch_packed)
+            L.hpk_encoded_len_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]
+            L.hpk_encoded_len_batch.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -262,6 +270,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_pack_geometry"):
             L.hpk_test_pack_geometry.argtypes = [c_u32p, c_u32p]
             L.hpk_test_pack_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_enclen_geometry"):
+            L.hpk_test_enclen_geometry.argtypes = [c_u32p] * 3
+            L.hpk_test_enclen_geometry.restype = ctypes.c_int
         if hasattr(L, "hpk_test_encode_geometry"):
             L.hpk_test_encode_geometry.argtypes = [c_u32p] * 5
             L.hpk_test_encode_geometry.restype = ctypes.c_int

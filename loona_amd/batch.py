@@ -384,6 +384,63 @@ class HuffmanCodec:
         return out_blob, out_off, out_len, status
 
 
+    def encoded_len_device(self, in_blob, in_off, out_len=None, sync=False):
+        """hpk_encoded_len_batch: torch cuda tensors -> out_len, literal i's Huffman-encoded length in bytes
+        (hpk_huffman_encoded_len of it: ceil(code bits / 8), 0 for an empty literal), with no byte encoded:
+        the number the H-bit rule (RFC 7541 section 5.2, "Huffman only where strictly shorter") compares with
+        the raw length. A literal with bad offsets counts 0 and raises the sticky error."""
+        import torch
+
+        n = int(in_off.shape[0]) - 1
+        if n < 0:
+            raise ValueError("in_off needs n+1 >= 1 entries")
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=in_blob.device)
+        dev = self.device
+        pi, in_cap = _arg(in_blob, "in_blob", ("uint8",), 0, dev)
+        pio, _ = _arg(in_off, "in_off", _OFF_DTYPES, n + 1, dev)
+        pl, _ = _arg(out_len, "out_len", _OFF_DTYPES, n, dev)
+        self._follow()
+        flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        rc = self._L.hpk_encoded_len_batch(self._h, pi, in_cap, pio, ctypes.c_uint32(n), pl, flags)
+        _lib.check(rc, "hpk_encoded_len_batch")
+        return out_len
+
+    def encode_packed(self, in_blob, in_off, out_blob=None, out_off=None, out_len=None, status=None, sync=False):
+        """hpk_encode_batch_packed: torch cuda tensors -> (out_blob, out_off, out_len, status) with the encoded
+        bytes end to end in literal order: out_off (n + 1 entries, an output) is the exclusive sum of out_len,
+        literal i is out_blob[out_off[i] : out_off[i + 1]] and out_off[n] the encoded total, so the result
+        feeds decode_packed as it is. The bytes are encode_device's for regions that are large enough; status
+        is 0, or 5 (bad offsets, out_len 0), never 4. out_blob may have any capacity: the bytes below it are
+        written, and a synchronous call raises (HPK_E_NOSPACE) when out_off[n] passes it; after an async call
+        compare out_off[n] yourself. out_blob=None with sync=True: the lengths are computed first
+        (encoded_len_device) and one host read of their total sizes the blob exactly. out_blob=None otherwise:
+        hpk_encoded_bound of the input, which always suffices."""
+        import torch
+
+        n = int(in_off.shape[0]) - 1
+        dev = in_blob.device
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if out_blob is None:
+            if sync and n > 0:
+                # (synchronous: the total is read by torch on its current stream, which need not be the codec's)
+                self.encoded_len_device(in_blob, in_off, out_len=out_len, sync=True)
+                total = int((out_len[:n].to(torch.int64) & 0xFFFFFFFF).sum().item())
+                if total > _lib.HPK_MAX_OFFSET:  # (the call voids such a batch and writes no byte)
+                    total = 0
+                out_blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+            else:
+                out_blob = torch.empty(max((30 * int(in_blob.numel()) + 7) // 8, 1), dtype=torch.uint8, device=dev)
+        if out_off is None:
+            out_off = torch.empty(n + 1, dtype=torch.int32 if int(out_blob.numel()) < 2**31 else torch.uint32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        self._call(self._L.hpk_encode_batch_packed, "hpk_encode_batch_packed", in_blob, in_off, out_blob, out_off,
+                   out_len, status, True, sync)
+        return out_blob, out_off, out_len, status
+
+
 def _bound_offsets_torch(in_off, num, den, add):
     import torch
 

@@ -7,7 +7,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.41 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only)"
+#define HPK_VERSION "hpk 0.41 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions)"
 
 static thread_local std::string t_last_error;
 
@@ -593,6 +593,50 @@ extern "C" int hpk_encode_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_ca
                                 uint8_t* status, int flags) {
     return run_batch(hpk_launch_encode, c, in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status,
                      flags);
+}
+
+// The encoded lengths alone (include/hpk.h): the length pass of the packed encode, no scratch.
+extern "C" int hpk_encoded_len_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                                     uint32_t* out_len, int flags) {
+    if (int rc = check_call(c, !in_off || (n && !out_len), flags, n, "encoded-length call", nullptr, nullptr)) return rc;
+    if (n == 0) return HPK_E_OK;
+    if (!in_blob && in_cap) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    // (a blob of no bytes: the kernel's clamped loads still read one chunk, so give them one that exists)
+    if (!in_blob || !in_cap) in_blob = reinterpret_cast<const uint8_t*>(c->d_codes), in_cap = 0;
+    if (int rc = hpk_launch_enclen(c, in_blob, clamp_cap(in_cap), in_off, n, out_len, nullptr)) return rc;
+    return call_end(c, flags);
+}
+
+// The packed encode (include/hpk.h): the length pass writes out_len and status, the length scan out_off, and
+// the encode kernel's packed instantiation writes every literal at its final place, clipped at out_cap. The
+// only scratch is the scan's tile sums; the word after them is the scan's verdict on the total.
+extern "C" int hpk_encode_batch_packed(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
+                                       uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
+                                       uint32_t* out_len, uint8_t* status, int flags) {
+    if (int rc = check_call(c, !in_off || !out_off || (n && (!out_len || !status)), flags, n, "packed encode", nullptr,
+                            nullptr))
+        return rc;
+    if (n && ((!in_blob && in_cap) || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
+        return packed_end(c, out_off, out_cap, flags);
+    }
+    const size_t tmp = hpk_pack_tmp_bytes(n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->pk_tmp, tmp + 32}}))) return rc;
+    // (blobs of no bytes: addresses that exist for the kernels' base pointers; with a capacity of 0 no byte
+    // of them is written, and the input's clamped loads read one chunk of the code table)
+    if (!in_blob || !in_cap) in_blob = reinterpret_cast<const uint8_t*>(c->d_codes), in_cap = 0;
+    if (!out_blob || !out_cap) out_blob = s->pk_tmp.as<uint8_t>() + ((tmp + 15) & ~(size_t)15), out_cap = 0;
+    if ((rc = hpk_launch_enclen(c, in_blob, clamp_cap(in_cap), in_off, n, out_len, status))) return rc;
+    if ((rc = hpk_len_scan(c, out_len, n, out_off, s->pk_tmp.p))) return rc;
+    const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), out_off, out_len, status};
+    if ((rc = hpk_launch_encode_packed(c, b, hpk_len_scan_verdict(s->pk_tmp.p, n)))) return rc;
+    if ((rc = slot_commit(c, s))) return rc;
+    return packed_end(c, out_off + n, out_cap, flags);
 }
 
 // buffet's buffer arena (crates/buffet/src/bufpool/privatepool.rs:80-108): ONE anonymous mapping of

@@ -151,6 +151,22 @@ bool hpk_compact_wave(const hpk_ctx* c, uint32_t n);
 int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, uint32_t* long_list, uint32_t* cursor,
                               bool wave);
 int hpk_launch_encode(hpk_ctx* c, const hpk_batch& b);
+#ifdef HPK_DIAG
+// diagnostic build: hpk_encode2's phase cycles of the last HPK_ENCODE_CFG=9 launch, either form's (16 x u64 of
+// device memory, allocated at the first such launch; defined in hpk_encode.hip)
+extern unsigned long long* hpk_g_eprof;
+#endif
+// The packed encode's three steps (hpk_encode_batch_packed), on the ctx stream. The length pass: out_len[i] =
+// literal i's encoded bytes, 0 with bad offsets (sticky error flag; status, if not null, HPK_OK or
+// HPK_BAD_OFFSETS). The length scan (hpk_pack.hip): out_off (n + 1 entries) = the exclusive sum of len, all 0
+// when the total passes HPK_MAX_OFFSET (flag set); tmp: hpk_pack_tmp_bytes(n) bytes of device scratch, and
+// hpk_len_scan_verdict(tmp, n) the word in it that is then nonzero. The encode into b.out_off's exact regions,
+// clipped at b.out_cap, void_all that word.
+int hpk_launch_enclen(hpk_ctx* c, const uint8_t* in_blob, uint32_t in_cap, const uint32_t* in_off, uint32_t n,
+                      uint32_t* out_len, uint8_t* status);
+int hpk_len_scan(hpk_ctx* c, const uint32_t* len, uint32_t n, uint32_t* out_off, void* tmp);
+const unsigned long long* hpk_len_scan_verdict(const void* tmp, uint32_t n);
+int hpk_launch_encode_packed(hpk_ctx* c, const hpk_batch& b, const unsigned long long* void_all);
 // The bound layout (hpk_pack.hip): out[i] = sum over j < i of the 4-rounded decoded bound of literal j, mod
 // 2^32 (n + 1 entries); tmp: hpk_bound_tmp_bytes(n) bytes of device scratch.
 size_t hpk_bound_tmp_bytes(uint32_t n);

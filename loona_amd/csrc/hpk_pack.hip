@@ -110,6 +110,32 @@ struct LenElem {
     }
 };
 
+// The packed encode's element: literal i's encoded length as the length pass wrote it (checked there).
+struct EncLenElem {
+    const uint32_t* __restrict__ len;
+
+    __device__ __forceinline__ void tile(uint32_t n, uint32_t base, uint32_t* s, uint32_t (&v)[kK]) const {
+        const uint32_t t = threadIdx.x;
+#pragma unroll
+        for (uint32_t k = 0; k < kK; ++k) {
+            const uint32_t j = base + t + kT * k;
+            s[t + kT * k] = j < n ? len[j] : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < kK; ++k) v[k] = s[t * kK + k];
+    }
+    __device__ __forceinline__ uint64_t tile_sum(uint32_t n, uint32_t base, uint32_t*) const {
+        uint64_t acc = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kK; ++k) {
+            const uint32_t j = base + threadIdx.x + kT * k;
+            acc += j < n ? len[j] : 0u;
+        }
+        return acc;
+    }
+};
+
 struct PackArgs {
     PackSrc src;
     const uint32_t* src_off;
@@ -203,6 +229,16 @@ extern "C" int hpk_test_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t 
 }
 
 size_t hpk_pack_tmp_bytes(uint32_t n) { return hpkscan::tmp_bytes<uint64_t>(n); }
+
+int hpk_len_scan(hpk_ctx* c, const uint32_t* len, uint32_t n, uint32_t* out_off, void* tmp) {
+    hpkscan::launch<uint64_t>(c->stream, EncLenElem{len}, n, out_off, tmp, c->d_err);
+    HIP_TRY(hipGetLastError());
+    return HPK_E_OK;
+}
+
+const unsigned long long* hpk_len_scan_verdict(const void* tmp, uint32_t n) {
+    return static_cast<const unsigned long long*>(tmp) + hpkscan::tiles(n);  // (sums[nt], hpk_scan.h)
+}
 
 // dst_off = the exclusive sum of the n lengths (those passing src_cap counted 0), then the bytes end to
 // end into dst_blob's first min(dst_off[n], dst_cap) bytes. tmp: hpk_pack_tmp_bytes(n) of device scratch.
