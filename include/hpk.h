@@ -231,6 +231,47 @@ int hpk_encode_batch_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap,
                             uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
                             uint8_t* status, int flags);
 
+/* ---- batch encode, packed string literals: H bit, length prefix, shorter form ----------------
+ * What an HPACK encoder writes per string (RFC 7541 §5.2; encode_string_literal, crates/loona-hpack/src/
+ * encoder.rs:296-307): the payload's length as a 7-bit-prefix integer (§5.1; encode_integer_into,
+ * encoder.rs:93-122), 0x80 ORed into its first octet for the Huffman form, then the payload: the raw octets or
+ * their Huffman coding. policy[i] (n entries, or NULL = all HPK_STR_AUTO) picks literal i's form: */
+#define HPK_STR_AUTO     0  /* H-bit form iff the literal is non-empty and its Huffman encoding is strictly
+                               shorter than its raw bytes; else raw (put_string, hpack_ref.Encoder._string) */
+#define HPK_STR_RAW      1  /* always raw: byte-identical to encode_string_literal */
+#define HPK_STR_HUFFMAN  2  /* always the H-bit form (an empty literal is the single octet 0x80) */
+#define HPK_STR_VERBATIM 3  /* the bytes as they are, no prefix: representation octets the host has made final */
+/* Literal i's representation is out_blob[out_off[i] .. out_off[i+1]): under policies 0-2 the prefix (1 to 6
+ * octets) followed by the payload, under HPK_STR_VERBATIM the input bytes alone. out_len[i] is the whole
+ * representation, prefix included; out_off (n+1 entries, an OUTPUT) is the exclusive sum of out_len; status[i]
+ * is HPK_OK or HPK_BAD_OFFSETS. The chosen form can be read from out_blob[out_off[i]] & 0x80, and Huffman
+ * payload bytes are exactly hpk_encode_batch_packed's. Sizing: len + 6 bytes per literal always suffice unless
+ * the policy is HPK_STR_HUFFMAN, where hpk_encoded_bound(len) + 6 do.
+ * Capacity, errors and offsets as hpk_encode_batch_packed: out_cap may be any size; nothing is written at or
+ * past min(out_off[n], out_cap) nor outside the blob; HPK_E_NOSPACE from a synchronous call when out_off[n] >
+ * out_cap, and HPK_E_INVAL wins over it; n == 0 writes out_off[0] = 0; a literal whose input offsets decrease
+ * or pass in_cap, or whose policy is above 3, is void (HPK_BAD_OFFSETS, out_len 0, the sticky flag), every
+ * literal with status HPK_OK holds its complete representation, and this version voids no other literal; a
+ * total past HPK_MAX_OFFSET voids every literal, zeroes every out_off and writes no byte. The context's stream
+ * and per-stream scratch; always the launch path.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC; or HPK_PTR_HOST, synchronous: offsets and policies are
+ * checked on the host before anything is copied (HPK_E_INVAL, nothing written), the input is staged in one
+ * piece into grow-only scratch of the stream's slot, and exactly min(out_off[n], out_cap) bytes come back with
+ * out_off, out_len and status.
+ * How: the length pass (hpk_encoded_len_batch's kernel) and an elementwise form step write out_len and
+ * status, the length scan writes out_off, and one tile kernel writes prefixes, Huffman codes and raw bytes at
+ * their final places through an LDS image in whole 16-byte chunks. No intermediate blob; the input is read
+ * twice. A raw or verbatim literal larger than a tile (16 KiB of input) is copied by a whole workgroup, a
+ * Huffman one is coded by one lane. Cost of a bad batch as hpk_encode_batch_packed. */
+int hpk_encode_strings_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                              const uint8_t* policy, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
+                              uint32_t* out_len, uint8_t* status, int flags);
+/* The representations' lengths alone (out_len as above, 0 for a void literal, which sets the sticky flag), no
+ * byte written: hpk_encoded_len_batch with the form and the prefix applied. Device pointers only
+ * (HPK_PTR_DEVICE, optionally HPK_ASYNC). No scratch. */
+int hpk_string_len_batch(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                         const uint8_t* policy, uint32_t* out_len, int flags);
+
 /* Which decode kernel a context's batches use. All give identical results (the parity tests run
  * every case through each); they differ in speed. HPK_DECODE_AUTO (the default): the wave-fill kernel
  * for every batch (since round 6; it had been the workgroup-fill kernel below 4M literals). */
@@ -419,9 +460,13 @@ int hpk_henc_encode(hpk_henc* enc, const uint8_t* fields, const uint32_t* field_
 
 /* Many responses' header blocks at once: block b encodes headers [hdr_off[b], hdr_off[b+1]) (header j
  * as in hpk_henc_encode) with encoder encs[b]; the blocks of one encoder are encoded in list order.
- * The table logic runs on the host; every string literal of every Huffman-coding encoder goes
- * through ONE hpk_encode_batch on ctx (the CPU batch path when ctx is NULL), and the H-bit form is
- * used where strictly shorter: the bytes equal hpk_henc_encode's block by block. Results in
+ * The table logic runs on the host. With a ctx and at least one non-empty string of a Huffman-coding
+ * encoder, every representation of every block goes through ONE hpk_encode_strings_packed call on ctx
+ * (HPK_PTR_HOST): octets the host has made final as HPK_STR_VERBATIM, a string as HPK_STR_AUTO if its
+ * encoder Huffman-codes, else HPK_STR_RAW, and the call's output is the blocks end to end. Otherwise
+ * (ctx NULL: the library's CPU batch path; or nothing to Huffman-code) the blocks are assembled on the
+ * host. Either way the H-bit form is used where strictly shorter and the bytes equal hpk_henc_encode's
+ * block by block. Results in
  * library-allocated buffers: block b is bytes[block_off[b] .. block_off[b+1]). */
 typedef struct hpk_henc_out {
     uint8_t* bytes;
@@ -455,6 +500,11 @@ int hpk_test_encode_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32
  * the first unfinished literal's start, or where the previous stretch ended when a literal passed its end),
  * the literals it looks at per stretch, and the literal count up to which a batch runs in one workgroup. */
 int hpk_test_enclen_geometry(uint32_t* stretch_bytes, uint32_t* window_literals, uint32_t* one_wg_literals);
+/* Testing only: the string-literal emit kernel's geometry (hpk_encode_strings_packed): input bytes per tile,
+ * bytes of the LDS output image, literals per tile, and the literal count up to which a batch runs in one
+ * workgroup. Its tiles are cut by the encode kernel's rule on the representations' offsets. */
+int hpk_test_strings_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32_t* tile_literals,
+                              uint32_t* one_wg_literals);
 /* Testing only: how many decode calls of this context the small-call mode's persistent kernel has
  * answered (hpk_ctx_set_small_mode), so the tests can tell it ran. */
 uint64_t hpk_test_small_calls(const hpk_ctx* ctx);

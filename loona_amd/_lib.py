@@ -33,6 +33,12 @@ HPK_PTR_DEVICE = 0x1
 HPK_ASYNC = 0x2
 HPK_MAX_OFFSET = 0xFFFFFFDF  # offsets of one shard stay at or below this (hpk.h)
 
+# string-literal policies of hpk_encode_strings_packed (hpk.h)
+HPK_STR_AUTO = 0
+HPK_STR_RAW = 1
+HPK_STR_HUFFMAN = 2
+HPK_STR_VERBATIM = 3
+
 # every symbol include/hpk.h declares (tests/test_host.py checks the .so exports all of them)
 EXPORTS = (
     "hpk_decoded_bound",
@@ -54,6 +60,8 @@ EXPORTS = (
     "hpk_encode_batch",
     "hpk_encoded_len_batch",
     "hpk_encode_batch_packed",
+    "hpk_encode_strings_packed",
+    "hpk_string_len_batch",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -88,6 +96,7 @@ EXPORTS = (
     "hpk_test_pack_geometry",
     "hpk_test_encode_geometry",
     "hpk_test_enclen_geometry",
+    "hpk_test_strings_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
     "hpk_ctx_set_decode_kernel",
@@ -179,6 +188,14 @@ def lib() -> ctypes.CDLL:
             L.hpk_encoded_len_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]
             L.hpk_encoded_len_batch.restype = ctypes.c_int
+        if hasattr(L, "hpk_encode_strings_packed"):  # (likewise: no string-literal encode)
+            L.hpk_encode_strings_packed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            L.hpk_encode_strings_packed.restype = ctypes.c_int
+            L.hpk_string_len_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            L.hpk_string_len_batch.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -273,6 +290,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_enclen_geometry"):
             L.hpk_test_enclen_geometry.argtypes = [c_u32p] * 3
             L.hpk_test_enclen_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_strings_geometry"):
+            L.hpk_test_strings_geometry.argtypes = [c_u32p] * 4
+            L.hpk_test_strings_geometry.restype = ctypes.c_int
         if hasattr(L, "hpk_test_encode_geometry"):
             L.hpk_test_encode_geometry.argtypes = [c_u32p] * 5
             L.hpk_test_encode_geometry.restype = ctypes.c_int

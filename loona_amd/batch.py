@@ -440,6 +440,99 @@ class HuffmanCodec:
                    out_len, status, True, sync)
         return out_blob, out_off, out_len, status
 
+    def _strings_call(self, in_blob, in_off, policy, out_blob, out_off, out_len, status, device, sync):
+        dev = self.device if device else None
+        n = int(in_off.shape[0]) - 1
+        if n < 0:
+            raise ValueError("in_off needs n+1 >= 1 entries")
+        pi, in_cap = _arg(in_blob, "in_blob", ("uint8",), 0, dev)
+        pio, _ = _arg(in_off, "in_off", _OFF_DTYPES, n + 1, dev)
+        pp = None if policy is None else _arg(policy, "policy", ("uint8",), n, dev)[0]
+        pl, _ = _arg(out_len, "out_len", _OFF_DTYPES, n, dev)
+        if device:
+            self._follow()
+            flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        else:
+            flags = _lib.HPK_PTR_HOST
+        if out_blob is None:  # the lengths alone
+            rc = self._L.hpk_string_len_batch(self._h, pi, in_cap, pio, ctypes.c_uint32(n), pp, pl, flags)
+            _lib.check(rc, "hpk_string_len_batch")
+            return
+        po, out_cap = _arg(out_blob, "out_blob", ("uint8",), 0, dev)
+        poo, _ = _arg(out_off, "out_off", _OFF_DTYPES, n + 1, dev)
+        ps, _ = _arg(status, "status", ("uint8",), n, dev)
+        rc = self._L.hpk_encode_strings_packed(self._h, pi, in_cap, pio, ctypes.c_uint32(n), pp, po, out_cap, poo, pl,
+                                               ps, flags)
+        _lib.check(rc, "hpk_encode_strings_packed")
+
+    def string_len_device(self, in_blob, in_off, policy=None, out_len=None, sync=False):
+        """hpk_string_len_batch: torch cuda tensors -> out_len, the bytes of literal i's RFC 7541 section 5.2
+        representation under policy[i] (see encode_strings), prefix included, with no byte written. A literal
+        with bad offsets or a policy above 3 counts 0 and raises the sticky error."""
+        import torch
+
+        n = int(in_off.shape[0]) - 1
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=in_blob.device)
+        self._strings_call(in_blob, in_off, policy, None, None, out_len, None, True, sync)
+        return out_len
+
+    def encode_strings(self, in_blob, in_off, policy=None, out_blob=None, out_off=None, out_len=None, status=None,
+                       sync=False):
+        """hpk_encode_strings_packed: torch cuda tensors -> (out_blob, out_off, out_len, status) with every
+        literal's string-literal representation (RFC 7541 section 5.2) end to end in literal order: the length
+        prefix, 0x80 in its first octet for the Huffman form, then the payload. policy (uint8 per literal, or
+        None = all 0): 0 Huffman where strictly shorter, else raw (hpack_ref.Encoder._string); 1 always raw;
+        2 always Huffman; 3 the bytes as they are, no prefix. out_off (n + 1 entries, an output) is the
+        exclusive sum of out_len, out_len the whole representation; status is 0, or 5 (bad offsets or policy,
+        out_len 0). Capacity rules as encode_packed. out_blob=None with sync=True: the lengths are computed
+        first (string_len_device) and one host read of their total sizes the blob exactly; out_blob=None
+        otherwise: a bound that always suffices (6 bytes per literal plus the input, or hpk_encoded_bound of it
+        when a policy array may force the Huffman form)."""
+        import torch
+
+        n = int(in_off.shape[0]) - 1
+        dev = in_blob.device
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if out_blob is None:
+            if sync and n > 0:
+                self.string_len_device(in_blob, in_off, policy, out_len=out_len, sync=True)
+                total = int((out_len[:n].to(torch.int64) & 0xFFFFFFFF).sum().item())
+                if total > _lib.HPK_MAX_OFFSET:  # (the call voids such a batch and writes no byte)
+                    total = 0
+                out_blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+            else:
+                nb = int(in_blob.numel())
+                bound = (nb if policy is None else max(nb, (30 * nb + 7) // 8)) + 6 * max(n, 0)
+                out_blob = torch.empty(max(bound, 1), dtype=torch.uint8, device=dev)
+        if out_off is None:
+            out_off = torch.empty(n + 1, dtype=torch.int32 if int(out_blob.numel()) < 2**31 else torch.uint32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        self._strings_call(in_blob, in_off, policy, out_blob, out_off, out_len, status, True, sync)
+        return out_blob, out_off, out_len, status
+
+    def encode_strings_host(self, in_blob, in_off, policy=None, out_cap=None):
+        """hpk_encode_strings_packed with host pointers: numpy in -> (out_blob, out_off, out_len, status),
+        staged through the context and synchronous. Offsets and policies are checked before anything is copied.
+        out_cap: the output's capacity (default: a bound that always suffices); the blob comes back cut to the
+        bytes written when the result fits, and the call raises (HPK_E_NOSPACE) when it does not."""
+        in_blob = np.ascontiguousarray(in_blob, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=U32)
+        policy = None if policy is None else np.ascontiguousarray(policy, dtype=np.uint8)
+        n = len(in_off) - 1
+        if out_cap is None:
+            out_cap = (in_blob.size if policy is None else max(in_blob.size, (30 * in_blob.size + 7) // 8)) + 6 * n
+        out_blob = np.zeros(max(int(out_cap), 1), dtype=np.uint8)[: int(out_cap)]
+        out_off = np.zeros(n + 1, dtype=U32)
+        out_len = np.zeros(max(n, 1), dtype=U32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        if in_blob.size == 0:
+            in_blob = np.zeros(1, dtype=np.uint8)[:0]
+        self._strings_call(in_blob, in_off, policy, out_blob, out_off, out_len, status, False, True)
+        return out_blob[: int(out_off[n])], out_off, out_len[:n], status[:n]
+
 
 def _bound_offsets_torch(in_off, num, den, add):
     import torch

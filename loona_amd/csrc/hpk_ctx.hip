@@ -7,7 +7,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.41 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions)"
+#define HPK_VERSION "hpk 0.42 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload)"
 
 static thread_local std::string t_last_error;
 
@@ -173,7 +173,7 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (hpk_slot& s : c->slots) {
         if (s.ev_set) (void)hipEventSynchronize(s.ev);
-        for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp})
+        for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage})
             (void)hipFree(b->p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
@@ -635,6 +635,117 @@ extern "C" int hpk_encode_batch_packed(hpk_ctx* c, const uint8_t* in_blob, size_
     if ((rc = hpk_len_scan(c, out_len, n, out_off, s->pk_tmp.p))) return rc;
     const hpk_batch b{in_blob, clamp_cap(in_cap), in_off, n, out_blob, clamp_cap(out_cap), out_off, out_len, status};
     if ((rc = hpk_launch_encode_packed(c, b, hpk_len_scan_verdict(s->pk_tmp.p, n)))) return rc;
+    if ((rc = slot_commit(c, s))) return rc;
+    return packed_end(c, out_off + n, out_cap, flags);
+}
+
+// The string-literal lengths alone (include/hpk.h): the length pass and its form step, no scratch.
+extern "C" int hpk_string_len_batch(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                                    const uint8_t* policy, uint32_t* out_len, int flags) {
+    if (int rc = check_call(c, !in_off || (n && !out_len), flags, n, "string-length call", nullptr, nullptr)) return rc;
+    if (n == 0) return HPK_E_OK;
+    if (!in_blob && in_cap) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!in_blob || !in_cap) in_blob = reinterpret_cast<const uint8_t*>(c->d_codes), in_cap = 0;
+    int rc;
+    if ((rc = hpk_launch_enclen(c, in_blob, clamp_cap(in_cap), in_off, n, out_len, nullptr)) ||
+        (rc = hpk_launch_strlen_form(c, clamp_cap(in_cap), in_off, n, policy, out_len, nullptr)))
+        return rc;
+    return call_end(c, flags);
+}
+
+// The string-literal encode's steps on device arrays (s: the stream's slot, pk_tmp reserved with tmp + 32
+// bytes): the length pass and its form step write out_len and status, the length scan out_off, and the emit
+// kernel every representation at its final place, clipped at out_cap.
+static int strings_steps(hpk_ctx* c, hpk_slot* s, size_t tmp, const uint8_t* in_blob, uint32_t in_cap,
+                         const uint32_t* in_off, uint32_t n, const uint8_t* policy, uint8_t* out_blob, uint32_t out_cap,
+                         uint32_t* out_off, uint32_t* out_len, uint8_t* status) {
+    // (blobs of no bytes: addresses that exist, as hpk_encode_batch_packed)
+    if (!in_blob || !in_cap) in_blob = reinterpret_cast<const uint8_t*>(c->d_codes), in_cap = 0;
+    if (!out_blob || !out_cap) out_blob = s->pk_tmp.as<uint8_t>() + ((tmp + 15) & ~(size_t)15), out_cap = 0;
+    int rc;
+    if ((rc = hpk_launch_enclen(c, in_blob, in_cap, in_off, n, out_len, nullptr)) ||
+        (rc = hpk_launch_strlen_form(c, in_cap, in_off, n, policy, out_len, status)) ||
+        (rc = hpk_len_scan(c, out_len, n, out_off, s->pk_tmp.p)))
+        return rc;
+    const hpk_batch b{in_blob, in_cap, in_off, n, out_blob, out_cap, out_off, out_len, status};
+    return hpk_launch_encode_strings(c, b, policy, hpk_len_scan_verdict(s->pk_tmp.p, n));
+}
+
+// The host form: offsets and policies checked before anything is copied, the input staged into the slot's
+// scratch in one piece, the steps, out_off[n] read back, then exactly the bytes written and the three arrays.
+static int strings_host(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                        const uint8_t* policy, uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
+                        uint8_t* status) {
+    if (check_offsets(in_off, n, in_cap)) return HPK_E_INVAL;
+    uint64_t bound = 0;  // no representation is longer: len + 6, or the Huffman bound + 6 where that form is forced
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t pol = policy ? policy[i] : (uint32_t)HPK_STR_AUTO, len = in_off[i + 1] - in_off[i];
+        if (pol > HPK_STR_VERBATIM) return hpk_set_err_msg("string policy above HPK_STR_VERBATIM", HPK_E_INVAL);
+        bound += (pol == HPK_STR_HUFFMAN ? hpk_encoded_bound(len) : (size_t)len) + 6u;
+    }
+    if (n == 0) {
+        out_off[0] = 0;
+        return HPK_E_OK;
+    }
+    const size_t in_bytes = in_off[n];
+    const uint32_t dcap = clamp_cap(bound < out_cap ? (size_t)bound : out_cap);
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t at_ioff = up16(in_bytes + 16), at_ooff = at_ioff + up16(4 * ((size_t)n + 1));
+    const size_t at_len = at_ooff + up16(4 * ((size_t)n + 1)), at_pol = at_len + up16(4 * (size_t)n);
+    const size_t at_st = at_pol + up16(n), at_out = at_st + up16(n);
+    const size_t tmp = hpk_pack_tmp_bytes(n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->pk_tmp, tmp + 32}, {&s->str_stage, at_out + (size_t)dcap + 16}})))
+        return rc;
+    uint8_t* d = s->str_stage.as<uint8_t>();
+    uint32_t* d_ioff = reinterpret_cast<uint32_t*>(d + at_ioff);
+    uint32_t* d_ooff = reinterpret_cast<uint32_t*>(d + at_ooff);
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d + at_len);
+    if (in_bytes > in_off[0])
+        HIP_TRY(hipMemcpyAsync(d + in_off[0], in_blob + in_off[0], in_bytes - in_off[0], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_ioff, in_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+    if (policy) HIP_TRY(hipMemcpyAsync(d + at_pol, policy, n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = strings_steps(c, s, tmp, d, (uint32_t)in_bytes, d_ioff, n, policy ? d + at_pol : nullptr, d + at_out, dcap,
+                            d_ooff, d_len, d + at_st)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out_off, d_ooff, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_len, d_len, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status, d + at_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t total = out_off[n], give = total < out_cap ? total : out_cap;
+    if (give) {
+        HIP_TRY(hipMemcpyAsync(out_blob, d + at_out, give, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if ((rc = slot_commit(c, s)) || (rc = take_err(c))) return rc;
+    if (total > out_cap) return hpk_set_err_msg("the packed bytes pass the output capacity", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The packed string-literal encode (include/hpk.h).
+extern "C" int hpk_encode_strings_packed(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off,
+                                         uint32_t n, const uint8_t* policy, uint8_t* out_blob, size_t out_cap,
+                                         uint32_t* out_off, uint32_t* out_len, uint8_t* status, int flags) {
+    if (!c || !in_off || !out_off || (n && (!out_len || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many literals for the string-literal encode", HPK_E_INVAL);
+    if (n && ((!in_blob && in_cap) || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!(flags & HPK_PTR_DEVICE))
+        return strings_host(c, in_blob, in_cap, in_off, n, policy, out_blob, out_cap, out_off, out_len, status);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
+        return packed_end(c, out_off, out_cap, flags);
+    }
+    const size_t tmp = hpk_pack_tmp_bytes(n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->pk_tmp, tmp + 32}}))) return rc;
+    if ((rc = strings_steps(c, s, tmp, in_blob, clamp_cap(in_cap), in_off, n, policy, out_blob, clamp_cap(out_cap),
+                            out_off, out_len, status)))
+        return rc;
     if ((rc = slot_commit(c, s))) return rc;
     return packed_end(c, out_off + n, out_cap, flags);
 }

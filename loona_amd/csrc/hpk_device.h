@@ -57,6 +57,8 @@ struct hpk_slot {
     // the packed form: the region decode's scratch blob and its bound layout, and the two scans' scratch (the
     // pack alone uses only the last)
     DevBuf pk_scratch, pk_bound, pk_tmp;
+    // the string-literal encode's host form: the staged input, arrays and output (hpk_encode_strings_packed)
+    DevBuf str_stage;
 };
 
 struct hpk_ctx {
@@ -167,6 +169,14 @@ int hpk_launch_enclen(hpk_ctx* c, const uint8_t* in_blob, uint32_t in_cap, const
 int hpk_len_scan(hpk_ctx* c, const uint32_t* len, uint32_t n, uint32_t* out_off, void* tmp);
 const unsigned long long* hpk_len_scan_verdict(const void* tmp, uint32_t n);
 int hpk_launch_encode_packed(hpk_ctx* c, const hpk_batch& b, const unsigned long long* void_all);
+// The string-literal encode's own steps (hpk_encode_strings.hip), on the ctx stream, around hpk_launch_enclen and
+// hpk_len_scan. The form step: out_len[i], literal i's Huffman bytes as hpk_launch_enclen left them, becomes the
+// length of its representation under policy[i] (null: all HPK_STR_AUTO), 0 with bad offsets or a policy above 3
+// (sticky error flag; status, if not null, HPK_OK or HPK_BAD_OFFSETS). The emit into b.out_off's exact regions,
+// clipped at b.out_cap, void_all the length scan's verdict.
+int hpk_launch_strlen_form(hpk_ctx* c, uint32_t in_cap, const uint32_t* in_off, uint32_t n, const uint8_t* policy,
+                           uint32_t* out_len, uint8_t* status);
+int hpk_launch_encode_strings(hpk_ctx* c, const hpk_batch& b, const uint8_t* policy, const unsigned long long* void_all);
 // The bound layout (hpk_pack.hip): out[i] = sum over j < i of the 4-rounded decoded bound of literal j, mod
 // 2^32 (n + 1 entries); tmp: hpk_bound_tmp_bytes(n) bytes of device scratch.
 size_t hpk_bound_tmp_bytes(uint32_t n);

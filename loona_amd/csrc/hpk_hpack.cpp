@@ -1060,10 +1060,11 @@ extern "C" int hpk_henc_encode(hpk_henc* e, const uint8_t* fields, const uint32_
 
 // Many response header blocks at once (the batched form of encoder.rs:210-234): the
 // table logic runs per block on the host, in order per encoder (it never depends on how a string
-// is coded); every string literal of every block whose encoder Huffman-codes is then encoded in
-// ONE batch (hpk_encode_batch through ctx, or the library's CPU batch path), and each block is
-// assembled with the H-bit form wherever it is strictly shorter — the same bytes as hpk_henc_encode
-// block by block.
+// is coded); then, through ctx, every representation of every block is one item of ONE
+// hpk_encode_strings_packed call whose output is the blocks end to end; without a ctx every string
+// literal of every block whose encoder Huffman-codes is encoded in ONE batch on the library's CPU batch
+// path and each block is assembled on the host. Either way the H-bit form is used wherever it is strictly
+// shorter — the same bytes as hpk_henc_encode block by block.
 // Test hook (include/hpk.h): the next n Huffman batches made by hpk_henc_encode_blocks fail as a
 // device error would, so tests can check that a failed call leaves every encoder as it was.
 static thread_local int t_fail_batches = 0;
@@ -1139,9 +1140,60 @@ extern "C" int hpk_henc_encode_blocks(hpk_ctx* ctx, hpk_henc* const* encs, const
         }
         ops_off[b + 1] = (uint32_t)ops.size();
     }
-    // pass 2: one Huffman batch for the strings of Huffman-coding encoders (u32 offsets: the strings
-    // and their encoded bounds must each fit below HPK_MAX_OFFSET)
     const uint32_t ns = (uint32_t)s_at.size();
+    bool any_huff = false;
+    for (uint32_t k = 0; k < ns; ++k) any_huff |= s_huff[k] != 0;
+    if (ctx && any_huff) {
+        // pass 2 on the device: every op in order is one item of ONE hpk_encode_strings_packed call, final
+        // representation octets as HPK_STR_VERBATIM, a string as HPK_STR_AUTO if its encoder Huffman-codes,
+        // else HPK_STR_RAW. The call's output is the blocks end to end: there is no pass 3.
+        const size_t ni = ops.size();
+        std::vector<uint32_t> in_off(ni + 1, 0), o_off(ni + 1), o_len(ni);
+        std::vector<uint8_t> in, pol(ni), ist(ni);
+        uint64_t hs = 0, eo_sum = 0;  // (the u32-range rule of the host path below, on the same strings)
+        for (size_t q = 0; q < ni; ++q) {
+            const Op& op = ops[q];
+            if (op.str == UINT32_MAX) {
+                in.insert(in.end(), raw.begin() + op.raw_at, raw.begin() + op.raw_at + op.raw_len);
+                pol[q] = HPK_STR_VERBATIM;
+            } else {
+                const uint32_t k = op.str;
+                in.insert(in.end(), fields + s_at[k], fields + s_at[k] + s_len[k]);
+                pol[q] = s_huff[k] ? HPK_STR_AUTO : HPK_STR_RAW;
+                if (s_huff[k]) {
+                    hs += s_len[k];
+                    eo_sum += (hpk_encoded_bound(s_len[k]) + 3) & ~(uint64_t)3;
+                }
+            }
+            if (hs > HPK_MAX_OFFSET || eo_sum > HPK_MAX_OFFSET || in.size() + 6 * (q + 1) > HPK_MAX_OFFSET)
+                return hpk_set_err_msg("Huffman strings of one call exceed the u32 offset range", HPK_E_INVAL);
+            in_off[q + 1] = (uint32_t)in.size();
+        }
+        if (t_fail_batches > 0) {
+            --t_fail_batches;
+            return hpk_set_err_msg("injected batch failure (hpk_test_fail_batches)", HPK_E_DEVICE);
+        }
+        const size_t cap = in.size() + 6 * ni;
+        out->block_off = (uint32_t*)malloc((nblocks + 1) * sizeof(uint32_t));
+        out->bytes = (uint8_t*)malloc(cap);
+        if (!out->block_off || !out->bytes) {
+            hpk_henc_out_free(out);
+            return HPK_E_INVAL;
+        }
+        if (int rc = hpk_encode_strings_packed(ctx, in.data(), in.size(), in_off.data(), (uint32_t)ni, pol.data(),
+                                               out->bytes, cap, o_off.data(), o_len.data(), ist.data(), HPK_PTR_HOST)) {
+            hpk_henc_out_free(out);
+            return rc;
+        }
+        for (uint32_t b = 0; b <= nblocks; ++b) out->block_off[b] = o_off[ops_off[b]];
+        out->n_blocks = nblocks;
+        out->len = o_off[ni];
+        for (const auto& kv : slot) *kv.first = std::move(work[kv.second]);
+        return HPK_E_OK;
+    }
+    // pass 2 on the host (no context, or no string to Huffman-code): one Huffman batch for the strings of
+    // Huffman-coding encoders (u32 offsets: the strings and their encoded bounds must each fit below
+    // HPK_MAX_OFFSET)
     std::vector<uint32_t> bi(ns, UINT32_MAX);  // string -> batch index
     std::vector<uint32_t> in_off(1, 0), eo(1, 0);
     std::vector<uint8_t> in;
@@ -1166,10 +1218,8 @@ extern "C" int hpk_henc_encode_blocks(hpk_ctx* ctx, hpk_henc* const* encs, const
             --t_fail_batches;
             rc = hpk_set_err_msg("injected batch failure (hpk_test_fail_batches)", HPK_E_DEVICE);
         } else {
-            rc = ctx ? hpk_encode_batch(ctx, in.data(), in.size(), in_off.data(), nb, enc.data(), enc.size(), eo.data(),
-                                        elen.data(), est.data(), HPK_PTR_HOST)
-                     : hpk_encode_batch_cpu(in.data(), in_off.data(), nb, enc.data(), eo.data(), elen.data(), est.data(),
-                                            0);
+            // (no context: with one, these strings went through the device path above)
+            rc = hpk_encode_batch_cpu(in.data(), in_off.data(), nb, enc.data(), eo.data(), elen.data(), est.data(), 0);
         }
         if (rc) return rc;
     }

@@ -206,9 +206,10 @@ class Encoder:
 
 def encode_blocks(pairs, codec=None):
     """[(Encoder, [(name, value)])] -> [block bytes]: the table logic per block on the host (blocks of
-    one encoder in list order), every string literal of every Huffman-coding encoder in ONE
-    hpk_encode_batch on `codec`'s device (the library's CPU batch path when codec is None); the same
-    bytes as Encoder.encode block by block (hpk_henc_encode_blocks)."""
+    one encoder in list order), every representation of every block through ONE
+    hpk_encode_strings_packed call on `codec`'s device, which frames each string and takes the Huffman form
+    where it is strictly shorter (the library's CPU batch path and a host assembly when codec is None); the
+    same bytes as Encoder.encode block by block (hpk_henc_encode_blocks)."""
     L = _lib.lib()
     parts, off, hoff = [], [0], [0]
     for _, headers in pairs:
