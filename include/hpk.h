@@ -41,9 +41,15 @@ typedef enum hpk_status {
     HPK_INVALID_PADDING = 2,    /* HuffmanDecoderError::InvalidPadding   (residual != EOS MSBs) */
     HPK_EOS_IN_STRING = 3,      /* HuffmanDecoderError::EOSInString      (30-bit EOS decoded) */
     HPK_OUTPUT_OVERFLOW = 4,    /* not a reference error: caller's out capacity < decoded size */
-    HPK_BAD_OFFSETS = 5         /* not a reference error: device-pointer call whose offsets are not
+    HPK_BAD_OFFSETS = 5,        /* not a reference error: device-pointer call whose offsets are not
                                    non-decreasing or pass a blob's capacity; the call's results are
                                    void (see hpk_decode_batch) */
+    /* hpk_decode_strings_packed only: decode_string's errors before any Huffman work (decoder.rs:67-143).
+       As hpk_block_error they are HPK_BLK_INT_TOO_MANY_OCTETS (2), HPK_BLK_INT_NOT_ENOUGH_OCTETS (4) and
+       HPK_BLK_STR_NOT_ENOUGH_OCTETS (6), in this order. */
+    HPK_PREFIX_TOO_MANY_OCTETS = 6,   /* IntegerDecodingError::TooManyOctets: continuation bit on the 5th octet */
+    HPK_PREFIX_NOT_ENOUGH_OCTETS = 7, /* IntegerDecodingError::NotEnoughOctets: empty window, or it ends inside the integer */
+    HPK_STRING_NOT_ENOUGH_OCTETS = 8  /* StringDecodingError::NotEnoughOctets: consumed + len passes the window */
 } hpk_status;
 
 /* ---- API return codes (negative = the call itself failed) -------------- */
@@ -271,6 +277,45 @@ int hpk_encode_strings_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_ca
  * (HPK_PTR_DEVICE, optionally HPK_ASYNC). No scratch. */
 int hpk_string_len_batch(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
                          const uint8_t* policy, uint32_t* out_len, int flags);
+
+/* ---- batch decode, packed string literals: prefix, H bit, raw or Huffman ---------------------
+ * The mirror of hpk_encode_strings_packed and the batch form of decode_string (crates/loona-hpack/src/
+ * decoder.rs:135-163): string i is decode_string(&in_blob[str_off[i] .. str_end[i]]), that is the length as a
+ * 7-bit-prefix integer (decode_integer, decoder.rs:67-125; non-canonical forms such as 7f 80 00 are accepted, as
+ * there), the check that prefix octets + length stay inside the window, then the payload: borrowed as it is, or
+ * Huffman-decoded when the first octet's 0x80 is set. The window may be longer than the string (the reference
+ * passes "the rest of the block"), and windows of different strings may overlap or coincide. str_end == NULL is
+ * the mirror form: str_off then has n + 1 entries and string i's window is [str_off[i], str_off[i+1]), which is
+ * hpk_encode_strings_packed's out_off as it stands.
+ * Outputs as hpk_decode_batch_packed: out_off (n + 1 entries, an OUTPUT) is the exclusive sum of out_len and
+ * string i's bytes are out_blob[out_off[i] .. out_off[i+1]) with no gap. A raw string's bytes are its payload
+ * verbatim (status HPK_OK); a Huffman string's bytes, out_len and status are exactly hpk_decode_batch's for its
+ * payload (an error literal keeps the bytes decoded before its error). consumed (n entries, may be NULL): the
+ * prefix octets + the payload length of every string whose prefix and length check passed, Huffman errors
+ * included; otherwise 0. A string that fails before its payload has out_len 0, consumed 0 and status
+ * HPK_PREFIX_TOO_MANY_OCTETS (reported whether or not more bytes follow the 5th octet),
+ * HPK_PREFIX_NOT_ENOUGH_OCTETS or HPK_STRING_NOT_ENOUGH_OCTETS; the call itself still returns HPK_E_OK.
+ * Capacity, HPK_E_NOSPACE, n == 0 and what is left unwritten as hpk_decode_batch_packed: out_cap may be any
+ * size, nothing is written at or past min(out_off[n], out_cap) nor outside the blob, the arrays are complete
+ * either way, and HPK_E_INVAL wins over HPK_E_NOSPACE. A string with str_off[i] > str_end[i] or str_end[i] >
+ * in_cap (mirror form: decreasing offsets, or past in_cap) is void: HPK_BAD_OFFSETS, out_len 0, consumed 0, the
+ * sticky flag; it voids no other string. hpk_decoded_bound(in_cap) + 4 n must not pass HPK_MAX_OFFSET
+ * (HPK_E_INVAL). The Huffman payloads' total can pass in_cap only when payloads overlap: the sticky flag is then
+ * set and the call's Huffman results are void in hpk_decode_batch's sense (those cut off get HPK_BAD_OFFSETS);
+ * overlapping windows whose decoded total passes HPK_MAX_OFFSET zero every out_off, write no byte and set the
+ * flag. Nothing outside [in_blob, in_blob + in_cap) is ever read, and of a window only the integer's octets and
+ * the payload.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC; or HPK_PTR_HOST, synchronous: the windows are checked on the
+ * host before anything is copied (HPK_E_INVAL, nothing written), the input is staged in one piece into grow-only
+ * scratch of the stream's slot, and exactly min(out_off[n], out_cap) bytes come back with out_off, out_len,
+ * consumed and status. Always the launch path: the small-call mode does not answer it.
+ * How: a parse kernel (one thread per string), the ordered pack gathering the Huffman payloads into a contiguous
+ * blob, hpk_decode_batch_packed's region decode of it (no decode kernel changes), an elementwise merge, the scan
+ * of out_len, and the ordered pack with a source per string (the region scratch or the input blob). Scratch per
+ * stream: hpk_decode_batch_packed's, plus in_cap bytes and 18 bytes per string. */
+int hpk_decode_strings_packed(hpk_ctx* ctx, const uint8_t* in_blob, size_t in_cap, const uint32_t* str_off,
+                              const uint32_t* str_end, uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off,
+                              uint32_t* out_len, uint32_t* consumed, uint8_t* status, int flags);
 
 /* Which decode kernel a context's batches use. All give identical results (the parity tests run
  * every case through each); they differ in speed. HPK_DECODE_AUTO (the default): the wave-fill kernel

@@ -21,6 +21,10 @@ HPK_INVALID_PADDING = 2
 HPK_EOS_IN_STRING = 3
 HPK_OUTPUT_OVERFLOW = 4
 HPK_BAD_OFFSETS = 5  # device-pointer call with decreasing offsets / offsets past a capacity
+# hpk_decode_strings_packed only: decode_string's errors before any Huffman work (decoder.rs:67-143)
+HPK_PREFIX_TOO_MANY_OCTETS = 6  # IntegerDecodingError::TooManyOctets
+HPK_PREFIX_NOT_ENOUGH_OCTETS = 7  # IntegerDecodingError::NotEnoughOctets
+HPK_STRING_NOT_ENOUGH_OCTETS = 8  # StringDecodingError::NotEnoughOctets
 
 HPK_E_OK = 0
 HPK_E_INVAL = -1
@@ -62,6 +66,7 @@ EXPORTS = (
     "hpk_encode_batch_packed",
     "hpk_encode_strings_packed",
     "hpk_string_len_batch",
+    "hpk_decode_strings_packed",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -196,6 +201,12 @@ def lib() -> ctypes.CDLL:
             L.hpk_string_len_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
             L.hpk_string_len_batch.restype = ctypes.c_int
+        if hasattr(L, "hpk_decode_strings_packed"):  # (likewise: no string-literal decode)
+            L.hpk_decode_strings_packed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_int]
+            L.hpk_decode_strings_packed.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -533,6 +533,85 @@ class HuffmanCodec:
         self._strings_call(in_blob, in_off, policy, out_blob, out_off, out_len, status, False, True)
         return out_blob[: int(out_off[n])], out_off, out_len[:n], status[:n]
 
+    def _decode_strings_call(self, in_blob, str_off, str_end, out_blob, out_off, out_len, consumed, status, device, sync):
+        dev = self.device if device else None
+        n = int(str_off.shape[0]) - (1 if str_end is None else 0)
+        if n < 0:
+            raise ValueError("str_off needs n+1 >= 1 entries when str_end is None")
+        pi, in_cap = _arg(in_blob, "in_blob", ("uint8",), 0, dev)
+        pso, _ = _arg(str_off, "str_off", _OFF_DTYPES, n + (1 if str_end is None else 0), dev)
+        pse = None if str_end is None else _arg(str_end, "str_end", _OFF_DTYPES, n, dev)[0]
+        po, out_cap = _arg(out_blob, "out_blob", ("uint8",), 0, dev)
+        poo, _ = _arg(out_off, "out_off", _OFF_DTYPES, n + 1, dev)
+        pl, _ = _arg(out_len, "out_len", _OFF_DTYPES, n, dev)
+        pc = None if consumed is None else _arg(consumed, "consumed", _OFF_DTYPES, n, dev)[0]
+        ps, _ = _arg(status, "status", ("uint8",), n, dev)
+        if device:
+            self._follow()
+            flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        else:
+            flags = _lib.HPK_PTR_HOST
+        rc = self._L.hpk_decode_strings_packed(self._h, pi, in_cap, pso, pse, ctypes.c_uint32(n), po, out_cap, poo, pl, pc,
+                                               ps, flags)
+        _lib.check(rc, "hpk_decode_strings_packed")
+
+    def decode_strings(self, in_blob, str_off, str_end=None, out_blob=None, out_off=None, out_len=None, consumed=None,
+                       status=None, sync=False):
+        """hpk_decode_strings_packed: torch cuda tensors -> (out_blob, out_off, out_len, consumed, status). String
+        i is the reference's decode_string on the window in_blob[str_off[i] : str_end[i]] (RFC 7541 section 5.2:
+        the 7-bit-prefix length, the H bit, then the raw or the Huffman payload); the window may be longer than
+        the string, and windows may overlap. str_end=None is the mirror form: str_off has n + 1 entries and
+        string i's window is [str_off[i], str_off[i + 1]), encode_strings' out_off as it stands. The decoded
+        strings come back end to end: out_off (n + 1 entries, an output) is the exclusive sum of out_len. status
+        is decode_device's for a Huffman payload, 0 for a raw string, 5 for a void window, or 6 / 7 / 8 (the
+        length integer has too many octets / the window ends inside it / the payload passes the window), each
+        with out_len 0; consumed is the prefix octets + the payload length where the prefix and the length check
+        passed, else 0. Capacity rules as decode_packed. out_blob=None allocates hpk_decoded_bound(in_blob)
+        bytes (enough unless windows overlap), cut to out_blob[:total] when sync=True."""
+        import torch
+
+        n = int(str_off.shape[0]) - (1 if str_end is None else 0)
+        dev = in_blob.device
+        own = out_blob is None
+        if own:
+            out_blob = torch.empty(max((8 * int(in_blob.numel())) // 5, 1), dtype=torch.uint8, device=dev)
+        if out_off is None:
+            out_off = torch.empty(n + 1, dtype=torch.int32 if int(out_blob.numel()) < 2**31 else torch.uint32, device=dev)
+        if out_len is None:
+            out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if consumed is None:
+            consumed = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        self._decode_strings_call(in_blob, str_off, str_end, out_blob, out_off, out_len, consumed, status, True, sync)
+        if own and sync:
+            out_blob = out_blob[: int(out_off[n].item()) & 0xFFFFFFFF]
+        return out_blob, out_off, out_len, consumed, status
+
+    def decode_strings_host(self, in_blob, str_off, str_end=None, out_cap=None):
+        """hpk_decode_strings_packed with host pointers: numpy in -> (out_blob, out_off, out_len, consumed,
+        status), staged through the context and synchronous. The windows are checked before anything is copied.
+        out_cap: the output's capacity (default: the windows' decoded bounds, which always suffice); the blob
+        comes back cut to the bytes written when the result fits, and the call raises (HPK_E_NOSPACE) when it
+        does not."""
+        in_blob = np.ascontiguousarray(in_blob, dtype=np.uint8)
+        str_off = np.ascontiguousarray(str_off, dtype=U32)
+        str_end = None if str_end is None else np.ascontiguousarray(str_end, dtype=U32)
+        n = len(str_off) - (1 if str_end is None else 0)
+        if out_cap is None:
+            a = str_off[:n].astype(np.int64)
+            e = (str_off[1:] if str_end is None else str_end).astype(np.int64)
+            out_cap = int((np.maximum(e - a, 0) * 8 // 5).sum())
+        out_blob = np.zeros(max(int(out_cap), 1), dtype=np.uint8)[: int(out_cap)]
+        out_off = np.zeros(n + 1, dtype=U32)
+        out_len = np.zeros(max(n, 1), dtype=U32)
+        consumed = np.zeros(max(n, 1), dtype=U32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        if in_blob.size == 0:
+            in_blob = np.zeros(1, dtype=np.uint8)[:0]
+        self._decode_strings_call(in_blob, str_off, str_end, out_blob, out_off, out_len, consumed, status, False, True)
+        return out_blob[: int(out_off[n])], out_off, out_len[:n], consumed[:n], status[:n]
+
 
 def _bound_offsets_torch(in_off, num, den, add):
     import torch

@@ -7,7 +7,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.42 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload)"
+#define HPK_VERSION "hpk 0.43 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string)"
 
 static thread_local std::string t_last_error;
 
@@ -173,7 +173,8 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (hpk_slot& s : c->slots) {
         if (s.ev_set) (void)hipEventSynchronize(s.ev);
-        for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage})
+        for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage, &s.sd_meta,
+                          &s.sd_hblob, &s.sd_stage})
             (void)hipFree(b->p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
@@ -745,6 +746,145 @@ extern "C" int hpk_encode_strings_packed(hpk_ctx* c, const uint8_t* in_blob, siz
     if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->pk_tmp, tmp + 32}}))) return rc;
     if ((rc = strings_steps(c, s, tmp, in_blob, clamp_cap(in_cap), in_off, n, policy, out_blob, clamp_cap(out_cap),
                             out_off, out_len, status)))
+        return rc;
+    if ((rc = slot_commit(c, s))) return rc;
+    return packed_end(c, out_off + n, out_cap, flags);
+}
+
+// The string-literal decode's scratch on one stream's slot: the parse step's arrays and the gather's offsets in
+// sd_meta, the gathered Huffman blob, and what the packed decode uses (region scratch, bound layout, scans, list).
+struct strdec_scratch {
+    uint32_t *start, *hlen, *rlen, *hoff;
+    uint8_t *pst, *sel, *hblob;
+};
+
+// (stage: the bytes of the host form's staging buffer, 0 for device pointers)
+static int strdec_reserve(hpk_ctx* c, hpk_slot* s, uint32_t in_cap, uint32_t n, uint64_t need, size_t stage, strdec_scratch* k) {
+    size_t tmp = hpk_bound_tmp_bytes(n);  // (the scans follow each other: one scratch)
+    if (tmp < hpk_pack_tmp_bytes(n)) tmp = hpk_pack_tmp_bytes(n);
+    const size_t words = 4 * (size_t)n + 4;
+    if (int rc = slot_reserve(c, s, {{&s->long_list, 4 * (size_t)n}, {&s->pk_bound, 4 * ((size_t)n + 1)}, {&s->pk_tmp, tmp},
+                                     {&s->pk_scratch, (size_t)need + 64}, {&s->sd_meta, 4 * words + 2 * (size_t)n + 16},
+                                     {&s->sd_hblob, (size_t)in_cap + 64}, {&s->sd_stage, stage}}))
+        return rc;
+    uint32_t* m = s->sd_meta.as<uint32_t>();
+    k->start = m;
+    k->hlen = m + n;
+    k->rlen = m + 2 * (size_t)n;
+    k->hoff = m + 3 * (size_t)n;  // n + 1 entries
+    k->pst = reinterpret_cast<uint8_t*>(m + words);
+    k->sel = k->pst + n;
+    k->hblob = s->sd_hblob.as<uint8_t>();
+    return HPK_E_OK;
+}
+
+// The string-literal decode's steps on device arrays (hpk_decode_strings.hip has the list), s the stream's slot,
+// reserved by strdec_reserve. need: hpk_decoded_bound(in_cap) + 4 n, the region scratch's bytes.
+static int strdec_steps(hpk_ctx* c, hpk_slot* s, const strdec_scratch& k, uint64_t need, const uint8_t* in_blob,
+                        uint32_t in_cap, const uint32_t* str_off, const uint32_t* str_end, uint32_t n, uint8_t* out_blob,
+                        uint32_t out_cap, uint32_t* out_off, uint32_t* out_len, uint32_t* consumed, uint8_t* status) {
+    // (blobs of no bytes: addresses that exist for the kernels' base pointers; no byte of them is read or written)
+    if (!in_blob || !in_cap) in_blob = k.hblob, in_cap = 0;
+    if (!out_blob || !out_cap) out_blob = k.hblob, out_cap = 0;
+    uint8_t* region = s->pk_scratch.as<uint8_t>();
+    uint32_t* bound = s->pk_bound.as<uint32_t>();
+    int rc;
+    if ((rc = hpk_launch_strparse(c, in_blob, in_cap, str_off, str_end, n, k.start, k.hlen, k.rlen, k.pst, consumed)) ||
+        // the Huffman payloads end to end (the total passes in_cap only when payloads overlap: the gather then
+        // stops at in_cap, the decode meets offsets past its blob and the merge voids what was cut)
+        (rc = hpk_pack_launch(c, in_blob, in_cap, k.start, k.hlen, n, k.hblob, in_cap, k.hoff, s->pk_tmp.p, in_cap)) ||
+        (rc = hpk_bound_scan(c, k.hoff, n, bound, s->pk_tmp.p)))
+        return rc;
+    const hpk_batch b{k.hblob, in_cap, k.hoff, n, region, (uint32_t)need, bound, out_len, status};
+    if ((rc = hpk_launch_decode(c, b, s->long_list.as<uint32_t>())) ||
+        (rc = hpk_launch_strmerge(c, n, k.start, k.hlen, k.rlen, k.pst, k.hoff, bound, (uint32_t)need, out_len, status, k.sel)) ||
+        (rc = hpk_len_scan(c, out_len, n, out_off, s->pk_tmp.p)))
+        return rc;
+    return hpk_pack2_launch(c, region, (uint32_t)need, in_blob, in_cap, k.start, k.sel, n, out_blob, out_cap, out_off,
+                            HPK_MAX_OFFSET);
+}
+
+// The host form: windows checked before anything is copied, the input staged in one piece (the bytes from the
+// lowest window start to the highest window end) into the slot's scratch, the steps, out_off[n] read back, then
+// exactly the bytes written and the arrays.
+static int strdec_host(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* str_off, const uint32_t* str_end,
+                       uint32_t n, uint8_t* out_blob, size_t out_cap, uint32_t* out_off, uint32_t* out_len,
+                       uint32_t* consumed, uint8_t* status) {
+    const bool mirror = !str_end;
+    const uint32_t* end = mirror ? str_off + 1 : str_end;
+    uint64_t bound = 0;  // no string decodes to more than hpk_decoded_bound of its window
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (str_off[i] > end[i]) return hpk_set_err_msg("a string's window ends before it starts", HPK_E_INVAL);
+        if (end[i] > in_cap || end[i] > HPK_MAX_OFFSET) return hpk_set_err_msg("a string's window passes the blob's capacity", HPK_E_INVAL);
+        bound += hpk_decoded_bound(end[i] - str_off[i]);
+        lo = str_off[i] < lo ? str_off[i] : lo;
+        hi = end[i] > hi ? end[i] : hi;
+    }
+    if (n == 0) {
+        out_off[0] = 0;
+        return HPK_E_OK;
+    }
+    const uint32_t dev_in = hi;  // the staged blob's capacity (offsets stay absolute; nothing below lo is read)
+    const uint64_t need = (uint64_t)hpk_decoded_bound(dev_in) + 4ull * n;
+    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the string-literal decode's output would pass 4 GiB", HPK_E_INVAL);
+    const uint32_t dcap = clamp_cap(bound < out_cap ? (size_t)bound : out_cap);
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t at_off = up16((size_t)dev_in + 16), at_end = at_off + up16(4 * ((size_t)n + 1));
+    const size_t at_ooff = at_end + up16(4 * (size_t)n), at_len = at_ooff + up16(4 * ((size_t)n + 1));
+    const size_t at_con = at_len + up16(4 * (size_t)n), at_st = at_con + up16(4 * (size_t)n), at_out = at_st + up16(n);
+    hpk_slot* s;
+    strdec_scratch k;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = strdec_reserve(c, s, dev_in, n, need, at_out + (size_t)dcap + 16, &k))) return rc;
+    uint8_t* d = s->sd_stage.as<uint8_t>();
+    uint32_t* d_off = reinterpret_cast<uint32_t*>(d + at_off);
+    uint32_t* d_end = mirror ? d_off + 1 : reinterpret_cast<uint32_t*>(d + at_end);
+    uint32_t* d_ooff = reinterpret_cast<uint32_t*>(d + at_ooff);
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d + at_len);
+    uint32_t* d_con = reinterpret_cast<uint32_t*>(d + at_con);
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(d + lo, in_blob + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_off, str_off, 4 * ((size_t)n + (mirror ? 1 : 0)), hipMemcpyHostToDevice, c->stream));
+    if (!mirror) HIP_TRY(hipMemcpyAsync(d_end, str_end, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = strdec_steps(c, s, k, need, d, dev_in, d_off, d_end, n, d + at_out, dcap, d_ooff, d_len, d_con, d + at_st)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out_off, d_ooff, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_len, d_len, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (consumed) HIP_TRY(hipMemcpyAsync(consumed, d_con, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status, d + at_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t total = out_off[n], give = total < out_cap ? total : out_cap;
+    if (give) {
+        HIP_TRY(hipMemcpyAsync(out_blob, d + at_out, give, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if ((rc = slot_commit(c, s)) || (rc = take_err(c))) return rc;
+    if (total > out_cap) return hpk_set_err_msg("the packed bytes pass the output capacity", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The packed string-literal decode (include/hpk.h).
+extern "C" int hpk_decode_strings_packed(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* str_off,
+                                         const uint32_t* str_end, uint32_t n, uint8_t* out_blob, size_t out_cap,
+                                         uint32_t* out_off, uint32_t* out_len, uint32_t* consumed, uint8_t* status, int flags) {
+    if (!c || !out_off || (n && (!str_off || !out_len || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (n >= 0x7FFFFFFFu) return hpk_set_err_msg("too many strings for the string-literal decode", HPK_E_INVAL);
+    if (n && ((!in_blob && in_cap) || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!(flags & HPK_PTR_DEVICE))
+        return strdec_host(c, in_blob, in_cap, str_off, str_end, n, out_blob, out_cap, out_off, out_len, consumed, status);
+    const uint64_t need = (uint64_t)hpk_decoded_bound(clamp_cap(in_cap)) + 4ull * n;
+    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the string-literal decode's output would pass 4 GiB", HPK_E_INVAL);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(out_off, 0, 4, c->stream));
+        return packed_end(c, out_off, out_cap, flags);
+    }
+    hpk_slot* s;
+    strdec_scratch k;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) || (rc = strdec_reserve(c, s, clamp_cap(in_cap), n, need, 0, &k))) return rc;
+    if ((rc = strdec_steps(c, s, k, need, in_blob, clamp_cap(in_cap), str_off, str_end ? str_end : str_off + 1, n, out_blob,
+                           clamp_cap(out_cap), out_off, out_len, consumed, status)))
         return rc;
     if ((rc = slot_commit(c, s))) return rc;
     return packed_end(c, out_off + n, out_cap, flags);

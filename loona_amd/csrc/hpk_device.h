@@ -59,6 +59,9 @@ struct hpk_slot {
     DevBuf pk_scratch, pk_bound, pk_tmp;
     // the string-literal encode's host form: the staged input, arrays and output (hpk_encode_strings_packed)
     DevBuf str_stage;
+    // the string-literal decode (hpk_decode_strings_packed): the parse step's per-string arrays and the gather's
+    // offsets, the gathered Huffman blob, and the host form's staged input, arrays and output
+    DevBuf sd_meta, sd_hblob, sd_stage;
 };
 
 struct hpk_ctx {
@@ -188,5 +191,22 @@ int hpk_bound_scan(hpk_ctx* c, const uint32_t* in_off, uint32_t n, uint32_t* out
 size_t hpk_pack_tmp_bytes(uint32_t n);
 int hpk_pack_launch(hpk_ctx* c, const uint8_t* src_blob, uint32_t src_cap, const uint32_t* src_off, const uint32_t* src_len,
                     uint32_t n, uint8_t* dst_blob, uint32_t dst_cap, uint32_t* dst_off, void* tmp, uint64_t total_bound);
+
+// The string-literal decode's own steps (hpk_decode_strings.hip), on the ctx stream, around hpk_pack_launch,
+// hpk_bound_scan, hpk_launch_decode and hpk_len_scan. The parse: string i's window in_blob[str_off[i] .. str_end[i])
+// gives pst[i] (HPK_OK, HPK_BAD_OFFSETS with the sticky flag, or one of the three prefix and length errors),
+// start[i] (the payload's first byte), hlen[i] / rlen[i] (a Huffman / a raw payload's bytes, the other 0; both 0
+// unless pst is HPK_OK) and consumed[i] (if not null). The merge: out_len / status hold the region decode of the
+// gathered Huffman payloads (offsets hoff, regions bound, of region_cap bytes) and become the final ones; src
+// (in: start) becomes the offset of string i's bytes in the source sel[i] names (0 the region scratch, 1 the input
+// blob). The two-source pack: hpk_pack_launch's kernel with that choice per literal, dst_off given (n + 1).
+int hpk_launch_strparse(hpk_ctx* c, const uint8_t* in_blob, uint32_t in_cap, const uint32_t* str_off, const uint32_t* str_end,
+                        uint32_t n, uint32_t* start, uint32_t* hlen, uint32_t* rlen, uint8_t* pst, uint32_t* consumed);
+int hpk_launch_strmerge(hpk_ctx* c, uint32_t n, uint32_t* src, const uint32_t* hlen, const uint32_t* rlen, const uint8_t* pst,
+                        const uint32_t* hoff, const uint32_t* bound, uint32_t region_cap, uint32_t* out_len, uint8_t* status,
+                        uint8_t* sel);
+int hpk_pack2_launch(hpk_ctx* c, const uint8_t* src0, uint32_t cap0, const uint8_t* src1, uint32_t cap1, const uint32_t* src_off,
+                     const uint8_t* sel, uint32_t n, uint8_t* dst_blob, uint32_t dst_cap, const uint32_t* dst_off,
+                     uint64_t total_bound);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

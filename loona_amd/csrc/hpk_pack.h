@@ -7,7 +7,8 @@
 // over however many literals the chunk spans (empty ones skipped), and takes each literal's share from
 // the aligned source dwords that hold it, shifted into place by alignbit. Nothing here touches LDS
 // or global memory except through the pointers it is given, so tests/emu/pack_emu.cpp runs these
-// functions as they are on the host.
+// functions as they are on the host. pack2_chunk is pack_chunk with one of two source blobs per literal
+// (hpk_pack2 in hpk_decode_strings.hip; tests/emu/pack2_emu.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -84,6 +85,26 @@ __device__ __forceinline__ void pack_chunk(uint32_t acc[4], DP d, SP so, uint32_
         }
         const uint32_t e = nx < hi ? nx : hi;
         pack_segment(acc, cpos + (o - lo), cpos + (e - lo), so[k] + (o - d[k]), s);
+        o = e;
+    }
+}
+
+// pack_chunk with a source per literal (the string-literal decode's last step, hpk_decode_strings.hip): staged
+// literal k's bytes are taken from s1 where sel[k] is nonzero, else from s0; so[k] is its offset in that
+// source. Everything else as pack_chunk, so a chunk may mix bytes of both sources.
+template <class DP, class SP, class XP>
+__device__ __forceinline__ void pack2_chunk(uint32_t acc[4], DP d, SP so, XP sel, uint32_t cnt, uint32_t lo, uint32_t hi,
+                                            uint32_t cpos, const PackSrc& s0, const PackSrc& s1) {
+    uint32_t k = pack_upper(d, cnt + 1u, lo) - 1u;  // d[k] <= lo < d[k + 1]
+    uint32_t o = lo;
+    while (o < hi && k < cnt) {
+        const uint32_t nx = d[k + 1u];
+        if (nx <= o) {  // an empty literal
+            ++k;
+            continue;
+        }
+        const uint32_t e = nx < hi ? nx : hi;
+        pack_segment(acc, cpos + (o - lo), cpos + (e - lo), so[k] + (o - d[k]), sel[k] ? s1 : s0);
         o = e;
     }
 }

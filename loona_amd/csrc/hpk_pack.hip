@@ -148,6 +148,9 @@ struct PackArgs {
 
 constexpr uint32_t kPackLdsBytes = (2u * kPackLds + 4u) * 4u;
 
+// (hpk_pack2 in hpk_decode_strings.hip is this kernel's twin, with a source selector staged beside each window's
+// offsets: a fix to the tile loop or the window restaging below belongs in both)
+
 __global__ __launch_bounds__(kPackThreads) void hpk_pack(PackArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t pack_smem[];
     uint32_t* sd = pack_smem;                 // the window's dst_off, kPackLds + 1 entries
