@@ -550,6 +550,16 @@ int hpk_test_enclen_geometry(uint32_t* stretch_bytes, uint32_t* window_literals,
  * workgroup. Its tiles are cut by the encode kernel's rule on the representations' offsets. */
 int hpk_test_strings_geometry(uint32_t* tile_bytes, uint32_t* image_bytes, uint32_t* tile_literals,
                               uint32_t* one_wg_literals);
+/* Testing only: the geometry of the decode kernels' two phases behind the fills, for kernel `kind`
+ * (HPK_DECODE_FILL or HPK_DECODE_WAVE; anything else is HPK_E_INVAL). out13 is a buffer of 13 values:
+ * [0] the workgroup's threads (the lanes the huge-literal phase has), [1] the encoded bytes from which a literal
+ * is a huge one, [2] the huge literals a workgroup lists at most (further ones go to the long-literal phase),
+ * [3] the least bytes of a huge literal's piece, [4] the encoded bytes from which a literal goes to the
+ * long-literal phase and [5] from which it is listed at the front, [6] the long phase's input ring in dwords per
+ * lane, [7] the 16-byte chunks a lane loads per refill point, [8] the steps between refill points, [9] the list
+ * entries per claim, [10] the waves that decode, [11] a lane's output buffer in bytes, [12] the two-symbol table
+ * both phases walk with (2, 3 or 4: hpk_walk.h). The tests place their edge cases relative to these. */
+int hpk_test_decode_geometry(int kind, uint32_t* out13);
 /* Testing only: how many decode calls of this context the small-call mode's persistent kernel has
  * answered (hpk_ctx_set_small_mode), so the tests can tell it ran. */
 uint64_t hpk_test_small_calls(const hpk_ctx* ctx);

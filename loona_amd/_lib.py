@@ -102,6 +102,7 @@ EXPORTS = (
     "hpk_test_encode_geometry",
     "hpk_test_enclen_geometry",
     "hpk_test_strings_geometry",
+    "hpk_test_decode_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
     "hpk_ctx_set_decode_kernel",
@@ -304,6 +305,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_strings_geometry"):
             L.hpk_test_strings_geometry.argtypes = [c_u32p] * 4
             L.hpk_test_strings_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_decode_geometry"):
+            L.hpk_test_decode_geometry.argtypes = [ctypes.c_int, c_u32p]
+            L.hpk_test_decode_geometry.restype = ctypes.c_int
         if hasattr(L, "hpk_test_encode_geometry"):
             L.hpk_test_encode_geometry.argtypes = [c_u32p] * 5
             L.hpk_test_encode_geometry.restype = ctypes.c_int

@@ -266,6 +266,25 @@ int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, 
     return HPK_E_OK;
 }
 
+extern "C" int hpk_test_decode_geometry(int kind, uint32_t* out13) {
+    if (!out13 || (kind != HPK_DECODE_FILL && kind != HPK_DECODE_WAVE)) return HPK_E_INVAL;
+    using GW = GeoW<kWaveWin, kWaveImg, HPK_WAVE_TAB>;
+    out13[0] = kind == HPK_DECODE_WAVE ? GW::kBlock : Geo::kBlock;
+    out13[1] = HPK_HUGE_MIN;
+    out13[2] = kHugeMax;
+    out13[3] = kHugePieceMin;
+    out13[4] = HPK_LONG_MIN;
+    out13[5] = HPK_LONG_BIG;
+    out13[6] = HPK_LONG_RING;
+    out13[7] = HPK_LONG_CH;
+    out13[8] = HPK_LONG_U;
+    out13[9] = HPK_LONG_CLAIM;
+    out13[10] = HPK_LONG_WAVES;
+    out13[11] = HPK_LONG_OS;
+    out13[12] = kind == HPK_DECODE_WAVE ? HPK_WAVE_TAB : 2;  // huge_phase / long_phase's kTab
+    return HPK_E_OK;
+}
+
 int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b, uint32_t* long_list) {
     DecodeArgs a;
     decode_args(c, b, a);

@@ -5,8 +5,9 @@
 //      end (lit12_step<.., kMore>), LUT3 and LUT2 layouts, exact-bound regions back to back, lanes in
 //      reverse order (a stray byte past a region would hit an already decoded neighbour);
 //   2. the fill kernel's protocol (hpk_fill.h: LUT2, no second-byte offset stores);
-//   3. the huge-literal phase (hpk_huge.h): its per-piece functions (hpk_huge_piece.h) under the workgroup's protocol.
-// Test infrastructure only (tests/test_walk_emulation.py). Exit status 0 = no mismatch.
+//   3. the huge-literal phase (hpk_huge.h): its per-piece functions (hpk_huge_piece.h) under the workgroup's protocol,
+//      under the 12-bit tables and the 13-bit one; `--file` replays the placed cases of tests/decode_long_cases.py.
+// Test infrastructure only (tests/test_walk_emulation.py, tests/test_decode_long_cases.py). Exit status 0 = no mismatch.
 #include "shim.h"
 #include "hpk_walk.h"
 #include "hpk_huge_piece.h"
@@ -134,8 +135,107 @@ static int run_lanes(std::mt19937_64& rng, int nlit, int maxlen) {
 
 // The huge-literal phase (hpk_huge.h) piece by piece, with the workgroup's protocol replayed on the
 // host (pass 1 for every piece, fix rounds on a snapshot of the pieces' ends, the first terminal piece,
-// the scan, pass 2): literals of 8 KiB to 1 MiB, valid, EOS near the end or at a piece boundary, bad
-// and too-long padding, random bytes, in exact-bound regions between guard bytes.
+// the scan, pass 2) under table kTab (2 and 3: the 12-bit layouts; 4: the wave kernel's 13-bit table), one
+// literal in an exact-bound region between guard bytes, against the oracle. A fix loop that has not ended
+// after P + 2 rounds is a failure (each round settles at least the first mismatch for good: P - 1 suffice).
+struct HugeStat {
+    uint32_t rounds, nones, nrun, term, tc, P, PB, status, olen;  // nones: pieces before the terminal one whose lead
+                                                                  // walk ended; nrun: the longest run of them
+};
+
+template <int kTab>
+static int replay_huge(const std::vector<uint8_t>& enc, uint32_t lanes, uint32_t in_mis, uint32_t out_mis, int kind,
+                       long* fixes, HugeStat* hs) {
+    const uint32_t* lut = kTab == 4 ? T.lut13 : kTab == 3 ? T.lut3 : T.lut2;
+    int bad = 0;
+    const uint32_t nb = enc.size();
+    std::vector<uint8_t> inb(16 + in_mis + nb + 64, 0x5A);
+    memcpy(inb.data() + 16 + in_mis, enc.data(), nb);
+    const uint8_t* in_base = inb.data() + 16;  // (16-byte aligned)
+    const uint32_t last16 = (in_mis + nb - 1) >> 4;
+    auto ld16 = [&](uint32_t ci) {
+        uint4 v;
+        memcpy(&v, in_base + 16 * std::min(ci, last16), 16);
+        return v;
+    };
+    const uint32_t cap = nb * 8 / 5;
+    std::vector<uint8_t> outb(16 + out_mis + cap + 64, 0xEE);
+    uint8_t* out_base = outb.data() + 16;
+    auto st8 = [&](uint32_t g, uint64_t v) {
+        if (g % 8) printf("huge: unaligned 8-byte store\n");
+        memcpy(out_base + g, &v, 8);
+    };
+    auto st1 = [&](uint32_t x, uint8_t v) { out_base[x] = v; };
+    uint32_t P, PB, OV;
+    huge_geometry(nb, lanes, P, PB, OV);
+    std::vector<uint32_t> S(P), E(P), c(P), fl(P);
+    for (uint32_t k = 0; k < P; ++k) huge_pass1<kTab>(ld16, lut, T.lo, in_mis, nb, k, P, PB, OV, S[k], E[k], c[k], fl[k]);
+    std::vector<uint8_t> none(P);
+    for (uint32_t k = 0; k < P; ++k) none[k] = S[k] == kHugeNone;
+    uint32_t rounds = 0;
+    for (;; ++rounds) {
+        std::vector<uint32_t> from(P, kHugeNone);
+        bool any = false;
+        for (uint32_t k = 1; k < P; ++k)
+            if (!(fl[k - 1] & kHugeTerm) && E[k - 1] != kHugeNone && S[k] != E[k - 1]) from[k] = E[k - 1], any = true;
+        if (!any) break;
+        if (rounds > P + 2) {
+            printf("huge tab %d: the fix rounds of a literal of %u B (P %u) do not end\n", kTab, nb, P);
+            return 1;
+        }
+        for (uint32_t k = 1; k < P; ++k)
+            if (from[k] != kHugeNone) {
+                huge_refix<kTab>(ld16, lut, T.lo, in_mis, nb, k, P, PB, from[k], S[k], E[k], c[k], fl[k]);
+                ++*fixes;
+            }
+    }
+    uint32_t t = kHugeNone;
+    for (uint32_t k = 0; k < P && t == kHugeNone; ++k)
+        if (fl[k] & kHugeTerm) t = k;
+    if (t == kHugeNone) {
+        printf("huge tab %d: no terminal piece (%u B)\n", kTab, nb);
+        return 1;
+    }
+    uint32_t D = 0;
+    for (uint32_t k = 0; k <= t; ++k) {
+        huge_pass2<kTab>(ld16, lut, T.lo, in_mis, S[k], c[k], out_mis + D, st8, st1);
+        D += c[k];
+    }
+    const uint32_t olen = D, ost = fl[t] & 0xFFu;
+    if (hs) {
+        uint32_t nn = 0, run = 0, best = 0;
+        for (uint32_t k = 0; k < t; ++k) {
+            nn += none[k];
+            run = none[k] ? run + 1 : 0;
+            best = std::max(best, run);
+        }
+        *hs = HugeStat{rounds, nn, best, t, c[t], P, PB, ost, olen};
+    }
+    std::vector<uint8_t> ref(cap + 8);
+    size_t rl = 0;
+    const int rs = oracle_decode(enc.data(), nb, ref.data(), ref.size(), &rl);
+    const bool ok = rs == (int)ost && rl == olen && memcmp(ref.data(), out_base + out_mis, rl) == 0;
+    if (!ok && bad < 5)
+        printf("huge tab %d: literal of %u B kind %d (P %u, PB %u): status %u vs %d, length %u vs %zu\n", kTab, nb, kind, P, PB,
+               ost, rs, olen, rl);
+    bad += !ok;
+    for (uint32_t j = 16 + out_mis + cap; j < outb.size(); ++j)
+        if (outb[j] != 0xEE) {
+            if (bad < 5) printf("huge tab %d: guard byte %u written (%u B)\n", kTab, j, nb);
+            ++bad;
+            break;
+        }
+    for (uint32_t j = 0; j < 16 + out_mis; ++j)
+        if (outb[j] != 0xEE) {
+            if (bad < 5) printf("huge tab %d: byte before the region written (%u B)\n", kTab, nb);
+            ++bad;
+            break;
+        }
+    return bad;
+}
+
+// Random literals of 8 KiB to 1 MiB: valid, EOS near the end or at a piece boundary, bad and too-long
+// padding, random bytes; each replayed under the three tables.
 static int run_huge(std::mt19937_64& rng, int nlit, uint32_t lanes, long* fixes) {
     const char* text = "abcdefghijklmnopqrstuvwxyz0123456789-_=;,/.:ABC ";
     int bad = 0;
@@ -164,78 +264,50 @@ static int run_huge(std::mt19937_64& rng, int nlit, uint32_t lanes, long* fixes)
             if (kind == 3) enc.push_back(0xFF);  // padding too long
             if (kind == 4) enc.back() &= 0xF0;
         }
-        const uint32_t nb = enc.size();
         const uint32_t in_mis = rng() % 16, out_mis = rng() % 16;
-        std::vector<uint8_t> inb(16 + in_mis + nb + 64, 0x5A);
-        memcpy(inb.data() + 16 + in_mis, enc.data(), nb);
-        const uint8_t* in_base = inb.data() + 16;  // (16-byte aligned)
-        const uint32_t last16 = (in_mis + nb - 1) >> 4;
-        auto ld16 = [&](uint32_t ci) {
-            uint4 v;
-            memcpy(&v, in_base + 16 * std::min(ci, last16), 16);
-            return v;
-        };
-        const uint32_t cap = nb * 8 / 5;
-        std::vector<uint8_t> outb(16 + out_mis + cap + 64, 0xEE);
-        uint8_t* out_base = outb.data() + 16;
-        auto st8 = [&](uint32_t g, uint64_t v) {
-            if (g % 8) printf("huge: unaligned 8-byte store\n");
-            memcpy(out_base + g, &v, 8);
-        };
-        auto st1 = [&](uint32_t x, uint8_t v) { out_base[x] = v; };
-        uint32_t P, PB, OV;
-        huge_geometry(nb, lanes, P, PB, OV);
-        std::vector<uint32_t> S(P), E(P), c(P), fl(P);
-        for (uint32_t k = 0; k < P; ++k) huge_pass1<2>(ld16, T.lut2, T.lo, in_mis, nb, k, P, PB, OV, S[k], E[k], c[k], fl[k]);
-        for (int guard = 0;; ++guard) {
-            std::vector<uint32_t> from(P, kHugeNone);
-            bool any = false;
-            for (uint32_t k = 1; k < P; ++k)
-                if (!(fl[k - 1] & kHugeTerm) && E[k - 1] != kHugeNone && S[k] != E[k - 1]) from[k] = E[k - 1], any = true;
-            if (!any || guard > (int)P + 2) break;
-            for (uint32_t k = 1; k < P; ++k)
-                if (from[k] != kHugeNone) {
-                    huge_refix<2>(ld16, T.lut2, T.lo, in_mis, nb, k, P, PB, from[k], S[k], E[k], c[k], fl[k]);
-                    ++*fixes;
-                }
-        }
-        uint32_t t = kHugeNone;
-        for (uint32_t k = 0; k < P && t == kHugeNone; ++k)
-            if (fl[k] & kHugeTerm) t = k;
-        if (t == kHugeNone) {
-            printf("huge: no terminal piece (%u B)\n", nb);
-            ++bad;
-            continue;
-        }
-        uint32_t D = 0;
-        for (uint32_t k = 0; k <= t; ++k) {
-            huge_pass2<2>(ld16, T.lut2, T.lo, in_mis, S[k], c[k], out_mis + D, st8, st1);
-            D += c[k];
-        }
-        const uint32_t olen = D, ost = fl[t] & 0xFFu;
-        std::vector<uint8_t> ref(cap + 8);
-        size_t rl = 0;
-        const int rs = oracle_decode(enc.data(), nb, ref.data(), ref.size(), &rl);
-        const bool ok = rs == (int)ost && rl == olen && memcmp(ref.data(), out_base + out_mis, rl) == 0;
-        if (!ok && bad < 5)
-            printf("huge: literal of %u B kind %d (P %u, PB %u): status %u vs %d, length %u vs %zu\n", nb, kind, P, PB, ost, rs,
-                   olen, rl);
-        bad += !ok;
-        for (uint32_t j = 0; j < outb.size(); ++j)
-            if ((j < 16 + out_mis || j >= 16 + out_mis + std::max<uint32_t>(olen, 0)) && j >= 16 + out_mis + cap &&
-                outb[j] != 0xEE) {
-                if (bad < 5) printf("huge: guard byte %u written (%u B)\n", j, nb);
-                ++bad;
-                break;
-            }
-        for (uint32_t j = 0; j < 16 + out_mis; ++j)
-            if (outb[j] != 0xEE) {
-                if (bad < 5) printf("huge: byte before the region written (%u B)\n", nb);
-                ++bad;
-                break;
-            }
+        bad += replay_huge<2>(enc, lanes, in_mis, out_mis, kind, fixes, nullptr);
+        bad += replay_huge<3>(enc, lanes, in_mis, out_mis, kind, fixes, nullptr);
+        bad += replay_huge<4>(enc, lanes, in_mis, out_mis, kind, fixes, nullptr);
     }
     return bad;
+}
+
+// `emu --file PATH LANES TAB`: the literals of a file written by tests/decode_long_cases.py (u32 count, then per
+// literal u32 bytes and the bytes, little-endian) through the huge phase's replay with LANES lanes under table
+// TAB; one line per literal: its fix rounds, the pieces before the terminal one whose lead walk ended, the
+// terminal piece and its count (none, and run: the longest run of such pieces).
+static int run_file(const char* path, uint32_t lanes, int tab) {
+    FILE* f = fopen(path, "rb");
+    uint32_t n = 0;
+    if (!f || fread(&n, 4, 1, f) != 1) {
+        printf("cannot read %s\n", path);
+        return 1;
+    }
+    int bad = 0;
+    long fixes = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t nb = 0;
+        if (fread(&nb, 4, 1, f) != 1 || nb == 0 || nb >= kHugeLimit) {
+            printf("bad literal header in %s\n", path);
+            return 1;
+        }
+        std::vector<uint8_t> enc(nb);
+        if (fread(enc.data(), 1, nb, f) != nb) {
+            printf("short file %s\n", path);
+            return 1;
+        }
+        HugeStat hs{};
+        const uint32_t in_mis = (7u * i) % 16u, out_mis = (5u * i + 3u) % 16u;
+        const int b = tab == 4   ? replay_huge<4>(enc, lanes, in_mis, out_mis, -1, &fixes, &hs)
+                      : tab == 3 ? replay_huge<3>(enc, lanes, in_mis, out_mis, -1, &fixes, &hs)
+                                 : replay_huge<2>(enc, lanes, in_mis, out_mis, -1, &fixes, &hs);
+        bad += b;
+        printf("lit %u bytes %u P %u PB %u rounds %u none %u run %u term %u c %u status %u len %u %s\n", i, nb, hs.P, hs.PB, hs.rounds,
+               hs.nones, hs.nrun, hs.term, hs.tc, hs.status, hs.olen, b ? "MISMATCH" : "ok");
+    }
+    fclose(f);
+    printf("%s: %d mismatches\n", bad ? "FAIL" : "ok", bad);
+    return bad != 0;
 }
 
 int main(int argc, char** argv) {
@@ -243,6 +315,7 @@ int main(int argc, char** argv) {
         printf("table build failed\n");
         return 1;
     }
+    if (argc == 5 && strcmp(argv[1], "--file") == 0) return run_file(argv[2], (uint32_t)atoi(argv[3]), atoi(argv[4]));
     std::mt19937_64 rng(argc > 1 ? atoi(argv[1]) : 1);
     const int iters = argc > 2 ? atoi(argv[2]) : 8;
     int bad = 0;

@@ -5,7 +5,8 @@ lit12_body, lit12_step with its end detection, lit12_load/status, lo_decode; hpk
 huge-literal phase's per-piece functions); tests/emu/shim.h, included first, stands in for the handful
 of HIP builtins they use (alignbit, clz). tests/emu/emu.cpp replays the kernels' per-lane protocols — the
 wave kernel's body steps then both tails (LUT3 and LUT2), the fill kernel's (LUT2), the huge-literal
-phase's passes and fix rounds — on random literals (text, 5-bit-only text that reaches the decoded
+phase's passes and fix rounds (under LUT2, LUT3 and the wave kernel's 13-bit table; a fix loop that does not
+end within P + 2 rounds fails) — on random literals (text, 5-bit-only text that reaches the decoded
 bound, random bytes, EOS runs, bad and too-long padding) in exact-bound regions back to back, against
 the oracle (oracle/hpk_oracle.c, the checker). What it cannot cover — LDS, waves, the fills' staging —
 is the GPU suite's job (tests/test_gpu.py)."""
