@@ -429,6 +429,73 @@ int hpk_hdec_decode_blocks(hpk_ctx* ctx, hpk_hdec* const* decs, const uint8_t* b
                            uint32_t nblocks, hpk_blocks_out* out);
 void hpk_blocks_out_free(hpk_blocks_out* out);
 
+/* ---- HPACK header blocks: the table-free scan on the device -------------------------------
+ * hpk_scan_blocks tokenises many header blocks at once — block b is blocks[block_off[b] .. block_off[b+1]) —
+ * with no decoder in hand: the batch form of the table-free half of Decoder::decode_with_cb (crates/loona-hpack/
+ * src/decoder.rs:368-450; decode_literal :502-527; decode_integer :67-125; decode_string's framing :135-143).
+ * Where the fields and strings of a block lie never depends on table state. Per field it gives the kind from
+ * the first octet (1xxxxxxx indexed, 7-bit prefix; 01 literal with incremental indexing, 6; 001 size update, 5;
+ * 0001 never indexed, 4; 0000 plain, 4), decode_integer's value (at most 5 octets; non-canonical forms are
+ * accepted, as there), and for a literal its strings: a name string only when the index is 0, then the value
+ * string, each framed against the rest of the block with the length comparison in 64 bits. A block's walk stops
+ * at its end or at its first integer or length error, which is recorded in the block's last field with the stage
+ * at which the reference would raise it. A string's payload is never read, and nothing outside
+ * [blocks, blocks + cap) and of a block nothing outside the block.
+ * Outputs: field_off and str_blk_off (nblocks + 1 entries each, exclusive sums: field_off[nblocks] is the field
+ * total, str_blk_off[nblocks] the string total); block b's records are fields[field_off[b] .. field_off[b+1])
+ * and its strings str_blk_off[b] .. str_blk_off[b+1] of the call's string list. The list is in block order, then
+ * field order, name before value; a string is listed only if its prefix and its length check passed, and its
+ * window [str_off[s], str_end[s]) is exact: from the first prefix octet to the payload's last byte. str_off and
+ * str_end are hpk_decode_strings_packed's inputs as they stand. A string whose framing failed is not listed: its
+ * field carries err and err_stage. status[b] is HPK_OK or HPK_BAD_OFFSETS.
+ * Capacities: fields_cap (records) and strs_cap (windows) may be any size; cap of each always suffices. Records
+ * and windows below the capacities are written and nothing at or past them; both offset arrays and status are
+ * complete either way. A synchronous call returns HPK_E_NOSPACE when a total passes its capacity; HPK_E_INVAL
+ * wins over HPK_E_NOSPACE. A block whose offsets decrease or pass cap is void: 0 fields, 0 strings,
+ * HPK_BAD_OFFSETS, the sticky flag; it voids no other block. cap above HPK_MAX_OFFSET is HPK_E_INVAL.
+ * nblocks == 0 writes the two zeros.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC (fields must then be 16-byte aligned: HPK_E_INVAL); or
+ * HPK_PTR_HOST, synchronous: the offsets are checked on the host before anything is copied (HPK_E_INVAL, nothing
+ * written), the input is staged in one piece into grow-only scratch of the stream's slot, and exactly the written
+ * parts come back. Always the launch path: the small-call mode does not answer it.
+ * How: a count pass (one lane per block, 256-lane workgroups: field count, string count, status), the length
+ * scan over each count array, and an emit pass (one lane per block again, the same walk: each record one 16-byte
+ * store). Both passes run the walk of hpk_blkscan.h, so they cannot disagree. Scratch per stream: 8 bytes per
+ * block and the scan's tile sums. Cost of a big block: one lane walks a whole block, two dependent byte loads per
+ * small field, so a block of many thousands of small fields takes that many load latencies whatever the rest of
+ * the batch does; blocks are not split. */
+typedef enum hpk_field_kind { HPK_FIELD_INDEXED = 0, HPK_FIELD_LIT_INCR = 1, HPK_FIELD_SIZE_UPDATE = 2,
+                              HPK_FIELD_LIT_NEVER = 3, HPK_FIELD_LIT_PLAIN = 4 } hpk_field_kind;
+typedef struct hpk_field {   /* 16 bytes */
+    uint32_t index;     /* header index / name index / new max size (decode_integer's value) */
+    uint32_t str;       /* index in the call's string list of this field's first listed string */
+    uint8_t  kind;      /* hpk_field_kind */
+    uint8_t  nstr;      /* strings of this field in the list: 0, 1 or 2 (name first) */
+    uint8_t  err;       /* hpk_block_error the scan found in this field, else 0; only a block's last field has one */
+    uint8_t  err_stage; /* 0 index, 1 name, 2 value: where the reference would raise err */
+    uint32_t at;        /* offset of the field's first octet in the blob */
+} hpk_field;
+
+int hpk_scan_blocks(hpk_ctx* ctx, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                    hpk_field* fields, size_t fields_cap, uint32_t* field_off,
+                    uint32_t* str_off, uint32_t* str_end, size_t strs_cap, uint32_t* str_blk_off,
+                    uint8_t* status, int flags);
+
+/* Where hpk_hdec_decode_blocks (and hpk_h2_read_frames, which calls it) scans a context's blocks.
+ * HPK_BLOCK_SCAN_HOST (the default): the two-pass path above. HPK_BLOCK_SCAN_DEVICE (opt-in; calls without a
+ * context are not affected): the blocks and block_off are uploaded once as they are; hpk_scan_blocks' kernels
+ * tokenise them; the two totals are read back; hpk_decode_strings_packed's pipeline decodes every listed string,
+ * raw and Huffman alike; the field records, field_off, the strings' out_off / out_len / status and the packed
+ * string bytes come back into the context's page-locked area; then the host applies the records in order per
+ * decoder, every string's bytes taken from the packed bytes. Results and decoder states equal the default
+ * path's exactly. The apply starts only when everything is back, so a device failure on this path leaves every
+ * decoder untouched. Known cost: raw strings travel to the device and back inside the packed bytes.
+ * Scratch per stream: the blocks, 16 bytes per field, 17 bytes per string and 12 per block, beside
+ * hpk_decode_strings_packed's. */
+#define HPK_BLOCK_SCAN_HOST 0    /* the default: the host scan */
+#define HPK_BLOCK_SCAN_DEVICE 1
+int hpk_ctx_set_block_scan(hpk_ctx* ctx, int kind);
+
 /* ---- HTTP/2 framing in front of the block decoder ------------------------
  * hpk_h2conn is one connection's header-reading state: its HPACK decoder and a HEADERS block still
  * waiting for CONTINUATION frames. hpk_h2_read_frames takes the bytes received on many
@@ -569,6 +636,9 @@ uint64_t hpk_test_small_calls(const hpk_ctx* ctx);
  * shader-clock cycles: offsets loaded, staged, walked, stored. out10 is a buffer of 10 values: the six
  * request stamps, then the four of the literal. */
 int hpk_test_small_stamps(const hpk_ctx* ctx, uint32_t* out10);
+/* Testing only: the block scan's geometry (hpk_scan_blocks): the blocks a workgroup of either pass walks, one
+ * per lane. The tests place their block counts relative to it. */
+int hpk_test_blkscan_geometry(uint32_t* wg_blocks);
 
 /* Library/kernel identification (for logs and the bench JSON). */
 const char* hpk_version(void);

@@ -37,6 +37,10 @@ HPK_PTR_DEVICE = 0x1
 HPK_ASYNC = 0x2
 HPK_MAX_OFFSET = 0xFFFFFFDF  # offsets of one shard stay at or below this (hpk.h)
 
+# hpk_ctx_set_block_scan (hpk.h)
+HPK_BLOCK_SCAN_HOST = 0
+HPK_BLOCK_SCAN_DEVICE = 1
+
 # string-literal policies of hpk_encode_strings_packed (hpk.h)
 HPK_STR_AUTO = 0
 HPK_STR_RAW = 1
@@ -67,6 +71,8 @@ EXPORTS = (
     "hpk_encode_strings_packed",
     "hpk_string_len_batch",
     "hpk_decode_strings_packed",
+    "hpk_scan_blocks",
+    "hpk_ctx_set_block_scan",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -105,6 +111,7 @@ EXPORTS = (
     "hpk_test_decode_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
+    "hpk_test_blkscan_geometry",
     "hpk_ctx_set_decode_kernel",
     "hpk_ctx_set_small_mode",
     "hpk_version",
@@ -208,6 +215,13 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_int]
             L.hpk_decode_strings_packed.restype = ctypes.c_int
+        if hasattr(L, "hpk_scan_blocks"):  # (likewise: no block scan)
+            L.hpk_scan_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+            L.hpk_scan_blocks.restype = ctypes.c_int
+            L.hpk_ctx_set_block_scan.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.hpk_ctx_set_block_scan.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -296,6 +310,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_bound_scan"):
             L.hpk_test_bound_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
             L.hpk_test_bound_scan.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_blkscan_geometry"):
+            L.hpk_test_blkscan_geometry.argtypes = [c_u32p]
+            L.hpk_test_blkscan_geometry.restype = ctypes.c_int
         if hasattr(L, "hpk_test_pack_geometry"):
             L.hpk_test_pack_geometry.argtypes = [c_u32p, c_u32p]
             L.hpk_test_pack_geometry.restype = ctypes.c_int

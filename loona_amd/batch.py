@@ -22,6 +22,9 @@ import numpy as np
 from . import _lib
 
 U32 = np.uint32
+# hpk_field (hpk.h): one 16-byte record of scan_blocks
+FIELD_DTYPE = np.dtype([("index", "<u4"), ("str", "<u4"), ("kind", "u1"), ("nstr", "u1"), ("err", "u1"),
+                        ("err_stage", "u1"), ("at", "<u4")])
 
 
 def pack(literals):
@@ -611,6 +614,91 @@ class HuffmanCodec:
             in_blob = np.zeros(1, dtype=np.uint8)[:0]
         self._decode_strings_call(in_blob, str_off, str_end, out_blob, out_off, out_len, consumed, status, False, True)
         return out_blob[: int(out_off[n])], out_off, out_len[:n], consumed[:n], status[:n]
+
+    BLOCK_SCANS = {"host": _lib.HPK_BLOCK_SCAN_HOST, "device": _lib.HPK_BLOCK_SCAN_DEVICE}
+
+    def set_block_scan(self, kind: str):
+        """'host' (the default) or 'device' (hpk_ctx_set_block_scan): where hpack.decode_blocks and
+        h2.read_frames scan this codec's header blocks. The same results; 'device' uploads the blocks as they are
+        and runs scan_blocks' kernels and decode_strings' pipeline before the host applies the records."""
+        if kind not in self.BLOCK_SCANS:
+            raise ValueError(f"block scan {kind!r} not in {tuple(self.BLOCK_SCANS)}")
+        _lib.check(self._L.hpk_ctx_set_block_scan(self._h, self.BLOCK_SCANS[kind]), "hpk_ctx_set_block_scan")
+
+    def _scan_blocks_call(self, blocks, block_off, fields, field_off, str_off, str_end, str_blk_off, status, device, sync):
+        dev = self.device if device else None
+        n = int(block_off.shape[0]) - 1
+        if n < 0:
+            raise ValueError("block_off needs nblocks+1 >= 1 entries")
+        pb, cap = _arg(blocks, "blocks", ("uint8",), 0, dev)
+        pbo, _ = _arg(block_off, "block_off", _OFF_DTYPES, n + 1, dev)
+        pf, fbytes = _arg(fields, "fields", ("uint8",), 0, dev)
+        pfo, _ = _arg(field_off, "field_off", _OFF_DTYPES, n + 1, dev)
+        pso, sbytes = _arg(str_off, "str_off", _OFF_DTYPES, 0, dev)
+        pse, ebytes = _arg(str_end, "str_end", _OFF_DTYPES, 0, dev)
+        psb, _ = _arg(str_blk_off, "str_blk_off", _OFF_DTYPES, n + 1, dev)
+        pst, _ = _arg(status, "status", ("uint8",), n, dev)
+        if device:
+            self._follow()
+            flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        else:
+            flags = _lib.HPK_PTR_HOST
+        rc = self._L.hpk_scan_blocks(self._h, pb, cap, pbo, ctypes.c_uint32(n), pf, fbytes // 16, pfo, pso, pse,
+                                     min(sbytes, ebytes) // 4, psb, pst, flags)
+        _lib.check(rc, "hpk_scan_blocks")
+
+    def scan_blocks(self, blocks, block_off, fields=None, field_off=None, str_off=None, str_end=None, str_blk_off=None,
+                    status=None, sync=False):
+        """hpk_scan_blocks: torch cuda tensors -> (fields, field_off, str_off, str_end, str_blk_off, status). Block
+        b is blocks[block_off[b] : block_off[b + 1]]; it is tokenised with no decoder in hand (the table-free half
+        of Decoder::decode_with_cb). fields is a uint8 tensor of 16-byte hpk_field records (view it with
+        FIELD_DTYPE on the host): block b's are records field_off[b] .. field_off[b + 1]. str_off / str_end are the
+        exact windows of the listed strings, block b's from str_blk_off[b]: decode_strings' inputs as they stand.
+        status[b] is 0, or 5 for a block with bad offsets. The capacities are the tensors' sizes (fields.numel() //
+        16 records, min(str_off, str_end) windows); what is allocated here holds len(blocks) of each, which always
+        suffices. With sync=True a list that does not fit raises (HPK_E_NOSPACE)."""
+        import torch
+
+        n = int(block_off.shape[0]) - 1
+        dev = blocks.device
+        m = max(int(blocks.numel()), 1)
+        if fields is None:
+            fields = torch.empty(16 * m, dtype=torch.uint8, device=dev)
+        if field_off is None:
+            field_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if str_off is None:
+            str_off = torch.empty(m, dtype=torch.int32, device=dev)
+        if str_end is None:
+            str_end = torch.empty(m, dtype=torch.int32, device=dev)
+        if str_blk_off is None:
+            str_blk_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        self._scan_blocks_call(blocks, block_off, fields, field_off, str_off, str_end, str_blk_off, status, True, sync)
+        return fields, field_off, str_off, str_end, str_blk_off, status
+
+    def scan_blocks_host(self, blocks, block_off, fields_cap=None, strs_cap=None):
+        """hpk_scan_blocks with host pointers: numpy in -> (fields, field_off, str_off, str_end, str_blk_off,
+        status), staged through the context and synchronous; fields is a FIELD_DTYPE record array. The offsets are
+        checked before anything is copied. fields_cap / strs_cap: the lists' capacities (default: the blocks'
+        bytes, which always suffice); the lists come back cut to their totals when they fit, and the call raises
+        (HPK_E_NOSPACE) when one does not."""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        block_off = np.ascontiguousarray(block_off, dtype=U32)
+        n = len(block_off) - 1
+        fcap = int(blocks.size if fields_cap is None else fields_cap)
+        scap = int(blocks.size if strs_cap is None else strs_cap)
+        fields = np.zeros(16 * max(fcap, 1), dtype=np.uint8)[: 16 * fcap]
+        str_off = np.zeros(max(scap, 1), dtype=U32)[:scap]
+        str_end = np.zeros(max(scap, 1), dtype=U32)[:scap]
+        field_off = np.zeros(n + 1, dtype=U32)
+        str_blk_off = np.zeros(n + 1, dtype=U32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        if blocks.size == 0:
+            blocks = np.zeros(1, dtype=np.uint8)[:0]
+        self._scan_blocks_call(blocks, block_off, fields, field_off, str_off, str_end, str_blk_off, status, False, True)
+        nf, ns = int(field_off[n]), int(str_blk_off[n])
+        return fields[: 16 * nf].view(FIELD_DTYPE), field_off, str_off[:ns], str_end[:ns], str_blk_off, status[:n]
 
 
 def _bound_offsets_torch(in_off, num, den, add):

@@ -3,11 +3,12 @@
 #include <string.h>
 #include <sys/mman.h>
 
+#include <chrono>
 #include <initializer_list>
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.43 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string)"
+#define HPK_VERSION "hpk 0.43 gfx950 decode v41 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail) and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block)"
 
 static thread_local std::string t_last_error;
 
@@ -174,7 +175,7 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     for (hpk_slot& s : c->slots) {
         if (s.ev_set) (void)hipEventSynchronize(s.ev);
         for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage, &s.sd_meta,
-                          &s.sd_hblob, &s.sd_stage})
+                          &s.sd_hblob, &s.sd_stage, &s.bs_meta, &s.bs_stage, &s.bs_out})
             (void)hipFree(b->p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
@@ -234,6 +235,14 @@ extern "C" int hpk_ctx_set_decode_kernel(hpk_ctx* c, int kind) {
     c->decode_kernel = kind;
     return HPK_E_OK;
 }
+
+extern "C" int hpk_ctx_set_block_scan(hpk_ctx* c, int kind) {
+    if (!c || (kind != HPK_BLOCK_SCAN_HOST && kind != HPK_BLOCK_SCAN_DEVICE)) return hpk_set_err_msg("bad block scan", HPK_E_INVAL);
+    c->block_scan = kind;
+    return HPK_E_OK;
+}
+
+int hpk_ctx_block_scan(const hpk_ctx* c) { return c ? c->block_scan : HPK_BLOCK_SCAN_HOST; }
 
 extern "C" void* hpk_ctx_stream(hpk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
@@ -888,6 +897,224 @@ extern "C" int hpk_decode_strings_packed(hpk_ctx* c, const uint8_t* in_blob, siz
         return rc;
     if ((rc = slot_commit(c, s))) return rc;
     return packed_end(c, out_off + n, out_cap, flags);
+}
+
+// The header-block scan's steps on device arrays (hpk_blkscan.hip has the list), s the stream's slot with
+// bs_meta (8 bytes per block) and pk_tmp (hpk_pack_tmp_bytes(nblocks)) reserved: the count pass and the two scans.
+// The emit pass is the caller's (the block decoder sizes its outputs by the totals before it emits).
+static int blkscan_counts(hpk_ctx* c, hpk_slot* s, const uint8_t* blocks, uint32_t cap, const uint32_t* block_off,
+                          uint32_t nblocks, uint32_t* field_off, uint32_t* str_blk_off, uint8_t* status) {
+    uint32_t* nf = s->bs_meta.as<uint32_t>();
+    uint32_t* ns = nf + nblocks;
+    int rc;
+    if ((rc = hpk_launch_blkcount(c, blocks, cap, block_off, nblocks, nf, ns, status)) ||
+        (rc = hpk_len_scan(c, nf, nblocks, field_off, s->pk_tmp.p)) ||
+        (rc = hpk_len_scan(c, ns, nblocks, str_blk_off, s->pk_tmp.p)))
+        return rc;
+    return HPK_E_OK;
+}
+
+static uint32_t clamp_u32(size_t x) { return x > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)x; }
+
+// The end of a scan call: a synchronous one reads both totals back with the wait, then reports bad offsets
+// (HPK_E_INVAL) before a list that did not fit (HPK_E_NOSPACE).
+static int blkscan_end(hpk_ctx* c, const uint32_t* field_off_n, size_t fields_cap, const uint32_t* str_blk_off_n,
+                       size_t strs_cap, int flags) {
+    if (flags & HPK_ASYNC) return HPK_E_OK;
+    uint32_t tot[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&tot[0], field_off_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&tot[1], str_blk_off_n, 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = call_end(c, flags)) return rc;
+    if ((size_t)tot[0] > fields_cap) return hpk_set_err_msg("the field records pass fields_cap", HPK_E_NOSPACE);
+    if ((size_t)tot[1] > strs_cap) return hpk_set_err_msg("the string windows pass strs_cap", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The host form: offsets checked before anything is copied, the blocks staged in one piece (at their own
+// offsets) into the slot's scratch beside the arrays, the steps, the totals read back, then exactly the written
+// records and windows and the three complete arrays.
+static int blkscan_host(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                        hpk_field* fields, size_t fields_cap, uint32_t* field_off, uint32_t* str_off, uint32_t* str_end,
+                        size_t strs_cap, uint32_t* str_blk_off, uint8_t* status) {
+    if (check_offsets(block_off, nblocks, cap)) return HPK_E_INVAL;
+    if (nblocks == 0) {
+        field_off[0] = 0;
+        str_blk_off[0] = 0;
+        return HPK_E_OK;
+    }
+    const uint32_t lo = block_off[0], hi = block_off[nblocks];
+    const uint32_t fcap = clamp_u32(fields_cap < hi - lo ? fields_cap : hi - lo);  // (a field and a string take an
+    const uint32_t scap = clamp_u32(strs_cap < hi - lo ? strs_cap : hi - lo);      // octet or more each)
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t offs = up16(4 * ((size_t)nblocks + 1));
+    const size_t at_boff = up16((size_t)hi + 16), at_foff = at_boff + offs, at_soff = at_foff + offs;
+    const size_t at_st = at_soff + offs, at_fields = at_st + up16(nblocks);
+    const size_t at_so = at_fields + 16 * (size_t)fcap, at_se = at_so + up16(4 * (size_t)scap);
+    const size_t bytes = at_se + up16(4 * (size_t)scap) + 16;
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->bs_meta, 8 * (size_t)nblocks}, {&s->pk_tmp, hpk_pack_tmp_bytes(nblocks)}, {&s->bs_stage, bytes}})))
+        return rc;
+    uint8_t* d = s->bs_stage.as<uint8_t>();
+    uint32_t* d_boff = reinterpret_cast<uint32_t*>(d + at_boff);
+    uint32_t* d_foff = reinterpret_cast<uint32_t*>(d + at_foff);
+    uint32_t* d_soff = reinterpret_cast<uint32_t*>(d + at_soff);
+    hpk_field* d_fields = reinterpret_cast<hpk_field*>(d + at_fields);
+    uint32_t* d_so = reinterpret_cast<uint32_t*>(d + at_so);
+    uint32_t* d_se = reinterpret_cast<uint32_t*>(d + at_se);
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(d + lo, blocks + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_boff, block_off, 4 * ((size_t)nblocks + 1), hipMemcpyHostToDevice, c->stream));
+    if ((rc = blkscan_counts(c, s, d, hi, d_boff, nblocks, d_foff, d_soff, d + at_st)) ||
+        (rc = hpk_launch_blkemit(c, d, hi, d_boff, nblocks, d_foff, d_soff, d_fields, fcap, d_so, d_se, scap)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(field_off, d_foff, 4 * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(str_blk_off, d_soff, 4 * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status, d + at_st, nblocks, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t nf = field_off[nblocks], ns = str_blk_off[nblocks];
+    const size_t gf = nf < fcap ? nf : fcap, gs = ns < scap ? ns : scap;
+    if (gf) HIP_TRY(hipMemcpyAsync(fields, d_fields, 16 * gf, hipMemcpyDeviceToHost, c->stream));
+    if (gs) {
+        HIP_TRY(hipMemcpyAsync(str_off, d_so, 4 * gs, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(str_end, d_se, 4 * gs, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (gf || gs) HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = slot_commit(c, s)) || (rc = take_err(c))) return rc;
+    if (nf > fields_cap) return hpk_set_err_msg("the field records pass fields_cap", HPK_E_NOSPACE);
+    if (ns > strs_cap) return hpk_set_err_msg("the string windows pass strs_cap", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The header-block scan (include/hpk.h).
+extern "C" int hpk_scan_blocks(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                               hpk_field* fields, size_t fields_cap, uint32_t* field_off, uint32_t* str_off,
+                               uint32_t* str_end, size_t strs_cap, uint32_t* str_blk_off, uint8_t* status, int flags) {
+    if (!c || !block_off || !field_off || !str_blk_off || (nblocks && !status)) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (nblocks >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the block scan", HPK_E_INVAL);
+    if (cap > HPK_MAX_OFFSET) return hpk_set_err_msg("the block scan's blob passes HPK_MAX_OFFSET", HPK_E_INVAL);
+    if (nblocks && ((!blocks && cap) || (!fields && fields_cap) || ((!str_off || !str_end) && strs_cap)))
+        return hpk_set_err_msg("null blob or list", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!(flags & HPK_PTR_DEVICE))
+        return blkscan_host(c, blocks, cap, block_off, nblocks, fields, fields_cap, field_off, str_off, str_end, strs_cap,
+                            str_blk_off, status);
+    if (((uintptr_t)fields & 15u) != 0) return hpk_set_err_msg("fields must be 16-byte aligned", HPK_E_INVAL);
+    if (nblocks == 0) {
+        HIP_TRY(hipMemsetAsync(field_off, 0, 4, c->stream));
+        HIP_TRY(hipMemsetAsync(str_blk_off, 0, 4, c->stream));
+        return blkscan_end(c, field_off, fields_cap, str_blk_off, strs_cap, flags);
+    }
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->bs_meta, 8 * (size_t)nblocks + 16}, {&s->pk_tmp, hpk_pack_tmp_bytes(nblocks)}})))
+        return rc;
+    // (a blob or a list of no capacity: an address that exists for the kernels' base pointers; nothing of it is touched)
+    if (!blocks || !cap) blocks = s->bs_meta.as<uint8_t>(), cap = 0;
+    if (!fields_cap) fields = reinterpret_cast<hpk_field*>(s->bs_meta.p);
+    if (!strs_cap) str_off = str_end = s->bs_meta.as<uint32_t>();
+    if ((rc = blkscan_counts(c, s, blocks, (uint32_t)cap, block_off, nblocks, field_off, str_blk_off, status)) ||
+        (rc = hpk_launch_blkemit(c, blocks, (uint32_t)cap, block_off, nblocks, field_off, str_blk_off, fields,
+                                 clamp_u32(fields_cap), str_off, str_end, clamp_u32(strs_cap))))
+        return rc;
+    if ((rc = slot_commit(c, s))) return rc;
+    return blkscan_end(c, field_off + nblocks, fields_cap, str_blk_off + nblocks, strs_cap, flags);
+}
+
+// The block decoder's device-scan path (hpk_hpack.cpp, HPK_BLOCK_SCAN_DEVICE; not in the C ABI): block_off is
+// non-decreasing (the caller's check). The blocks and block_off go up once as they are; the count pass and the
+// scans run and the two totals come back (the pipeline's one wait before its end); the outputs are sized by them;
+// the emit pass and hpk_decode_strings_packed's steps over every listed string follow; then the field records,
+// field_off and the strings' out_off / out_len / status come back into the context's page-locked area, and with
+// out_off's last entry known, exactly the packed bytes. Everything is on the host when this returns HPK_E_OK.
+int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o) {
+    *o = hpk_blkdev{};
+    if (nblocks == 0) return HPK_E_OK;
+    if (nblocks >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the block scan", HPK_E_INVAL);
+    const uint32_t lo = block_off[0], hi = block_off[nblocks];
+    if (hi > HPK_MAX_OFFSET) return hpk_set_err_msg("the blocks pass HPK_MAX_OFFSET", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [&](std::chrono::steady_clock::time_point a) {
+        return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
+    };
+    const auto t_0 = now();
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t offs = up16(4 * ((size_t)nblocks + 1));
+    const size_t at_boff = up16((size_t)hi + 16), at_foff = at_boff + offs, at_soff = at_foff + offs, at_st = at_soff + offs;
+    hpk_slot* s;
+    int rc;
+    if ((rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->bs_meta, 8 * (size_t)nblocks}, {&s->pk_tmp, hpk_pack_tmp_bytes(nblocks)},
+                                  {&s->bs_stage, at_st + up16(nblocks) + 16}})))
+        return rc;
+    uint8_t* d = s->bs_stage.as<uint8_t>();
+    uint32_t* d_boff = reinterpret_cast<uint32_t*>(d + at_boff);
+    uint32_t* d_foff = reinterpret_cast<uint32_t*>(d + at_foff);
+    uint32_t* d_soff = reinterpret_cast<uint32_t*>(d + at_soff);
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(d + lo, blocks + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_boff, block_off, 4 * ((size_t)nblocks + 1), hipMemcpyHostToDevice, c->stream));
+    if ((rc = blkscan_counts(c, s, d, hi, d_boff, nblocks, d_foff, d_soff, d + at_st))) return rc;
+    uint32_t tot[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&tot[0], d_foff + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&tot[1], d_soff + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t nf = tot[0], ns = tot[1];
+    o->us_scan = us(t_0);
+    const auto t_1 = now();
+    // the outputs, sized by the totals; the strings decode to no more than the blocks' decoded bound
+    const uint64_t need = (uint64_t)hpk_decoded_bound(hi) + 4ull * ns;
+    if (need > HPK_MAX_OFFSET) return hpk_set_err_msg("the blocks' strings would pass 4 GiB", HPK_E_INVAL);
+    const uint32_t dcap = (uint32_t)hpk_decoded_bound(hi) + 16u;
+    const size_t sw = up16(4 * ((size_t)ns + 1));
+    const size_t at_so = 16 * (size_t)nf, at_se = at_so + sw, at_oo = at_se + sw, at_ol = at_oo + sw, at_ss = at_ol + sw;
+    const size_t at_out = at_ss + up16(ns);
+    strdec_scratch k{};
+    if ((rc = slot_reserve(c, s, {{&s->bs_out, at_out + dcap + 16}}))) return rc;
+    if (ns && (rc = strdec_reserve(c, s, hi, ns, need, 0, &k))) return rc;
+    uint8_t* q = s->bs_out.as<uint8_t>();
+    hpk_field* d_fields = reinterpret_cast<hpk_field*>(q);
+    uint32_t* d_so = reinterpret_cast<uint32_t*>(q + at_so);
+    uint32_t* d_se = reinterpret_cast<uint32_t*>(q + at_se);
+    uint32_t* d_oo = reinterpret_cast<uint32_t*>(q + at_oo);
+    uint32_t* d_ol = reinterpret_cast<uint32_t*>(q + at_ol);
+    if ((rc = hpk_launch_blkemit(c, d, hi, d_boff, nblocks, d_foff, d_soff, d_fields, nf, d_so, d_se, ns))) return rc;
+    if (ns && (rc = strdec_steps(c, s, k, need, d, hi, d_so, d_se, ns, q + at_out, dcap, d_oo, d_ol, nullptr, q + at_ss)))
+        return rc;
+    // back into the page-locked area: fields | field_off | out_off | out_len | status | the packed bytes
+    const size_t h_foff = 16 * (size_t)nf, h_oo = h_foff + offs, h_ol = h_oo + sw, h_ss = h_ol + sw, h_out = h_ss + up16(ns);
+    uint8_t* h = nullptr;
+    if ((rc = hpk_ctx_pinned(c, h_out + dcap + 16, (void**)&h))) return rc;
+    if (nf) HIP_TRY(hipMemcpyAsync(h, d_fields, 16 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h + h_foff, d_foff, 4 * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, c->stream));
+    uint32_t* h_off = reinterpret_cast<uint32_t*>(h + h_oo);
+    h_off[0] = 0;
+    if (ns) {
+        HIP_TRY(hipMemcpyAsync(h_off, d_oo, 4 * ((size_t)ns + 1), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h + h_ol, d_ol, 4 * (size_t)ns, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h + h_ss, q + at_ss, ns, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    o->us_strings = us(t_1);
+    const auto t_2 = now();
+    const uint32_t total = h_off[ns];
+    if (total > dcap) return hpk_set_err_msg("the blocks' strings pass their decoded bound", HPK_E_DEVICE);
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(h + h_out, q + at_out, total, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if ((rc = slot_commit(c, s))) return rc;
+    o->fields = reinterpret_cast<const hpk_field*>(h);
+    o->field_off = reinterpret_cast<const uint32_t*>(h + h_foff);
+    o->out_off = h_off;
+    o->out_len = reinterpret_cast<const uint32_t*>(h + h_ol);
+    o->status = h + h_ss;
+    o->arena = h + h_out;
+    o->nfields = nf;
+    o->nstrs = ns;
+    o->us_back = us(t_2);
+    return HPK_E_OK;
 }
 
 // buffet's buffer arena (crates/buffet/src/bufpool/privatepool.rs:80-108): ONE anonymous mapping of

@@ -62,12 +62,16 @@ struct hpk_slot {
     // the string-literal decode (hpk_decode_strings_packed): the parse step's per-string arrays and the gather's
     // offsets, the gathered Huffman blob, and the host form's staged input, arrays and output
     DevBuf sd_meta, sd_hblob, sd_stage;
+    // the header-block scan (hpk_scan_blocks): the count pass's two arrays; the staged input and arrays of its host
+    // form and of the block decoder's device-scan path; and that path's outputs, sized once the totals are known
+    DevBuf bs_meta, bs_stage, bs_out;
 };
 
 struct hpk_ctx {
     int device = 0;
     int num_cu = 256;
     int decode_kernel = HPK_DECODE_AUTO;  // hpk_ctx_set_decode_kernel
+    int block_scan = HPK_BLOCK_SCAN_HOST;  // hpk_ctx_set_block_scan
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
     uint32_t* d_lut2 = nullptr;
@@ -208,5 +212,16 @@ int hpk_launch_strmerge(hpk_ctx* c, uint32_t n, uint32_t* src, const uint32_t* h
 int hpk_pack2_launch(hpk_ctx* c, const uint8_t* src0, uint32_t cap0, const uint8_t* src1, uint32_t cap1, const uint32_t* src_off,
                      const uint8_t* sel, uint32_t n, uint8_t* dst_blob, uint32_t dst_cap, const uint32_t* dst_off,
                      uint64_t total_bound);
+
+// The header-block scan's two passes (hpk_blkscan.hip), on the ctx stream, around hpk_len_scan. The count pass:
+// block b = blob[block_off[b] .. block_off[b+1]) gives nfields[b], nstrs[b] and status[b] (HPK_OK, or
+// HPK_BAD_OFFSETS with the sticky flag and both counts 0). The emit pass: the same walk, block b's records to
+// fields[field_off[b] ..) and its string windows to str_off / str_end from str_blk_off[b], each only below its
+// capacity; fields is 16-byte aligned.
+int hpk_launch_blkcount(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint32_t* block_off, uint32_t nblocks,
+                        uint32_t* nfields, uint32_t* nstrs, uint8_t* status);
+int hpk_launch_blkemit(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint32_t* block_off, uint32_t nblocks,
+                       const uint32_t* field_off, const uint32_t* str_blk_off, hpk_field* fields, uint32_t fields_cap,
+                       uint32_t* str_off, uint32_t* str_end, uint32_t strs_cap);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/hpk.h"
+#include "hpk_internal.h"  // hpk_blocks_device: the device-scan path
 
 int hpk_set_err_msg(const char* what, int code);  // hpk_ctx.hip: hpk_last_error's message
 // hpk_ctx.hip: the context's page-locked host staging area, grown to at least `bytes` (grow-only)
@@ -644,6 +645,193 @@ inline uint32_t dec_bucket(const hpk_hdec* d) {
     return (uint32_t)((((uintptr_t)d >> 4) * 0x9E3779B97F4A7C15ull) >> (64 - kBucketBits));
 }
 thread_local BlockScratch t_scratch;
+
+// buckets to threads, heaviest first onto the least loaded thread (W.bwork: [thread][bucket] -> W.bthread)
+void place_buckets(BlockScratch& W, int nth) {
+    uint64_t bsum[kBuckets];
+    uint16_t order[kBuckets];
+    for (int k = 0; k < kBuckets; ++k) {
+        uint64_t x = 0;
+        for (int t = 0; t < nth; ++t) x += W.bwork[(size_t)t * kBuckets + k];
+        bsum[k] = x;
+        order[k] = (uint16_t)k;
+    }
+    std::sort(order, order + kBuckets, [&](uint16_t x, uint16_t y) { return bsum[x] > bsum[y]; });
+    uint64_t load[Pool::kMax] = {};
+    W.bthread.resize(kBuckets);
+    for (int i = 0; i < kBuckets; ++i) {
+        int m = 0;
+        for (int t = 1; t < nth; ++t)
+            if (load[t] < load[m]) m = t;
+        load[m] += bsum[order[i]];
+        W.bthread[order[i]] = (uint8_t)m;
+    }
+}
+
+typedef std::function<void(const std::function<void(int)>&)> Parallel;
+
+// join the per-thread outputs (W.outs, W.owner) into the caller's buffers
+int join_outputs(BlockScratch& W, int nth, uint32_t nblocks, hpk_blocks_out* out, const Parallel& parallel) {
+    std::vector<Out>& outs = W.outs;
+    std::vector<uint8_t>& owner = W.owner;
+    hpk_block_result* res = out->blocks;
+    auto blk0 = [&](int t) { return (uint32_t)((uint64_t)nblocks * t / nth); };
+    std::vector<uint32_t>&abase = W.abase, &hbase = W.hbase;
+    abase.assign(nth, 0);
+    hbase.assign(nth, 0);
+    size_t at = 0, ht = 0;
+    for (int t = 0; t < nth; ++t) {
+        abase[t] = (uint32_t)at;
+        hbase[t] = (uint32_t)ht;
+        at += outs[t].an;
+        ht += outs[t].hn;
+    }
+    out->arena_len = at;
+    out->n_headers = ht;
+    out->arena = (uint8_t*)g_out_cache.take(0, at);
+    out->headers = (hpk_header*)g_out_cache.take(1, ht * sizeof(hpk_header));
+    if (at >= (1ull << 32) || !out->arena || !out->headers) {
+        hpk_blocks_out_free(out);
+        return HPK_E_INVAL;
+    }
+    parallel([&](int t) {
+        if (outs[t].an) memcpy(out->arena + abase[t], outs[t].arena.data(), outs[t].an);
+        for (size_t j = 0; j < outs[t].hn; ++j) {
+            hpk_header hd = outs[t].headers[j];
+            hd.name_off += abase[t];
+            hd.value_off += abase[t];
+            out->headers[hbase[t] + j] = hd;
+        }
+        for (uint32_t b = blk0(t); b < blk0(t + 1); ++b) res[b].first_header += hbase[owner[b]];
+    });
+    return HPK_E_OK;
+}
+}  // namespace
+
+namespace {
+
+// The device-scan path's pass 3 for one block (HPK_BLOCK_SCAN_DEVICE): apply_block's single pass over the public
+// hpk_field records of hpk_scan_blocks, every string's bytes and Huffman status taken from the packed string
+// decode's results (a raw string's status is HPK_OK). The order of the checks is apply_block's.
+void apply_block_dev(hpk_hdec* d, const hpk_field* fields, uint32_t nfields, const hpk_blkdev& h, Out& o,
+                     hpk_block_result* r) {
+    r->first_header = (uint32_t)o.hn;
+    r->n_headers = 0;
+    r->error = HPK_BLK_OK;
+    r->detail = 0;
+    auto fail = [&](int e, int detail) {
+        r->error = e;
+        r->detail = detail;
+    };
+    auto emit = [&](const uint8_t* n, size_t nl, const uint8_t* v, size_t vl) {
+        hpk_header hd;
+        hd.name_len = (uint32_t)nl;
+        hd.name_off = put(o, n, nl);
+        hd.value_len = (uint32_t)vl;
+        hd.value_off = put(o, v, vl);
+        put_header(o, hd);
+        r->n_headers += 1;
+        return hd;
+    };
+    bool last_was_size_update = false;
+    for (uint32_t fi = 0; fi < nfields; ++fi) {
+        const hpk_field& f = fields[fi];
+        last_was_size_update = f.kind == HPK_FIELD_SIZE_UPDATE;
+        if (f.err && f.err_stage == kStIndex) return fail(f.err, 0);
+        if (f.kind == HPK_FIELD_INDEXED) {
+            const uint8_t *n, *v;
+            size_t nl, vl;
+            if (!d->get(f.index, &n, &nl, &v, &vl)) return fail(HPK_BLK_HEADER_INDEX_OUT_OF_BOUNDS, 0);
+            emit(n, nl, v, vl);
+            continue;
+        }
+        if (f.kind == HPK_FIELD_SIZE_UPDATE) {  // update_max_dynamic_size (decoder.rs:538-554)
+            if (d->has_max_allowed && f.index > d->max_allowed) return fail(HPK_BLK_INVALID_MAX_DYNAMIC_SIZE, 0);
+            d->max_size = (size_t)f.index;
+            d->consolidate();
+            continue;
+        }
+        // literal: name (its string, the field's first listed one, or the table's name), then value
+        const uint8_t* np;
+        size_t nl;
+        uint32_t s = f.str;
+        if (f.index == 0) {
+            if (f.err && f.err_stage == kStName) return fail(f.err, 0);
+            if (int hs = h.status[s]) return fail(HPK_BLK_STR_HUFFMAN, hs);
+            np = h.arena + h.out_off[s];
+            nl = h.out_len[s];
+            s += 1;
+        } else {
+            const uint8_t* v;
+            size_t vl;
+            if (!d->get(f.index, &np, &nl, &v, &vl)) return fail(HPK_BLK_HEADER_INDEX_OUT_OF_BOUNDS, 0);
+        }
+        if (f.err && f.err_stage == kStValue) return fail(f.err, 0);
+        if (int hs = h.status[s]) return fail(HPK_BLK_STR_HUFFMAN, hs);
+        const hpk_header hd = emit(np, nl, h.arena + h.out_off[s], h.out_len[s]);
+        // (the insertion reads the header's copies in the output, as apply_block's)
+        if (f.kind == HPK_FIELD_LIT_INCR) d->add(o.arena.data() + hd.name_off, nl, o.arena.data() + hd.value_off, h.out_len[s]);
+    }
+    if (last_was_size_update) fail(HPK_BLK_SIZE_UPDATE_AT_END, 0);
+}
+
+// hpk_hdec_decode_blocks with HPK_BLOCK_SCAN_DEVICE (include/hpk.h has the steps): the device does the scan and
+// every string; the host threads apply once everything is back, so a device failure leaves every decoder as it
+// was. Placement as the default path's: a decoder's blocks on one thread, in order, buckets placed by the work
+// (fields + 1 per block) that field_off states.
+int decode_blocks_device(hpk_ctx* ctx, hpk_hdec* const* decs, const uint8_t* blocks, const uint32_t* block_off,
+                         uint32_t nblocks, hpk_blocks_out* out, int nth, const Parallel& parallel, bool timing) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [&](std::chrono::steady_clock::time_point a) {
+        return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
+    };
+    hpk_blkdev h;
+    if (int rc = hpk_blocks_device(ctx, blocks, block_off, nblocks, &h)) return rc;
+    auto t_2 = now();
+    BlockScratch& W = t_scratch;
+    if ((int)W.outs.size() < nth) W.outs.resize(nth);
+    W.bwork.assign((size_t)nth * kBuckets, 0);
+    W.bkt.resize(nblocks);
+    auto blk0 = [&](int t) { return (uint32_t)((uint64_t)nblocks * t / nth); };
+    parallel([&](int t) {
+        uint64_t* const bw = W.bwork.data() + (size_t)t * kBuckets;
+        for (uint32_t b = blk0(t); b < blk0(t + 1); ++b) {
+            const uint32_t k = dec_bucket(decs[b]);
+            W.bkt[b] = (uint16_t)k;
+            bw[k] += h.field_off[b + 1] - h.field_off[b] + 1u;
+        }
+    });
+    place_buckets(W, nth);
+    std::vector<Out>& outs = W.outs;
+    for (int t = 0; t < nth; ++t)
+        outs[t].reset(4 * (size_t)block_off[nblocks] / (size_t)nth + 4096, h.nfields / (size_t)nth + 16);
+    out->n_blocks = nblocks;
+    out->blocks = (hpk_block_result*)g_out_cache.take(2, (size_t)nblocks * sizeof(hpk_block_result));
+    if (!out->blocks) return HPK_E_INVAL;
+    hpk_block_result* res = out->blocks;
+    std::vector<uint8_t>& owner = W.owner;
+    owner.resize(nblocks);
+    parallel([&](int t) {
+        Out mine = std::move(outs[t]);  // (a local: no false sharing with the neighbours' headers)
+        const uint16_t* const bk = W.bkt.data();
+        const uint8_t* const bt = W.bthread.data();
+        for (uint32_t b = 0; b < nblocks; ++b) {
+            if (bt[bk[b]] != t) continue;
+            owner[b] = (uint8_t)t;
+            apply_block_dev(decs[b], h.fields + h.field_off[b], h.field_off[b + 1] - h.field_off[b], h, mine, &res[b]);
+        }
+        outs[t] = std::move(mine);
+    });
+    const long us_apply = us(t_2);
+    auto t_3 = now();
+    if (int rc = join_outputs(W, nth, nblocks, out, parallel)) return rc;
+    if (timing)
+        fprintf(stderr,
+                "hpk_hdec_decode_blocks: %d threads, device scan %ld us, strings %ld us, bytes back %ld us, apply %ld us, join %ld us\n",
+                nth, h.us_scan, h.us_strings, h.us_back, us_apply, us(t_3));
+    return HPK_E_OK;
+}
+
 }  // namespace
 
 // Timeline of a call with a device context: scan (threads) -> the batch assembled in the pinned
@@ -671,6 +859,8 @@ extern "C" int hpk_hdec_decode_blocks(hpk_ctx* ctx, hpk_hdec* const* decs, const
     auto us = [&](std::chrono::steady_clock::time_point a) {
         return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
     };
+    if (ctx && hpk_ctx_block_scan(ctx) == HPK_BLOCK_SCAN_DEVICE)  // opt-in: scan and strings on the device
+        return decode_blocks_device(ctx, decs, blocks, block_off, nblocks, out, nth, parallel, timing);
     // pass 1: scan every block, gather the Huffman strings (contiguous block ranges per thread)
     BlockScratch& W = t_scratch;
     std::vector<Scan>& scans = W.scans;
@@ -805,26 +995,7 @@ extern "C" int hpk_hdec_decode_blocks(hpk_ctx* ctx, hpk_hdec* const* decs, const
     hpk_block_result* res = out->blocks;
     std::vector<uint8_t>& owner = W.owner;
     owner.resize(nblocks);
-    {  // buckets to threads, heaviest first onto the least loaded thread
-        uint64_t bsum[kBuckets];
-        uint16_t order[kBuckets];
-        for (int k = 0; k < kBuckets; ++k) {
-            uint64_t x = 0;
-            for (int t = 0; t < nth; ++t) x += W.bwork[(size_t)t * kBuckets + k];
-            bsum[k] = x;
-            order[k] = (uint16_t)k;
-        }
-        std::sort(order, order + kBuckets, [&](uint16_t x, uint16_t y) { return bsum[x] > bsum[y]; });
-        uint64_t load[Pool::kMax] = {};
-        W.bthread.resize(kBuckets);
-        for (int i = 0; i < kBuckets; ++i) {
-            int m = 0;
-            for (int t = 1; t < nth; ++t)
-                if (load[t] < load[m]) m = t;
-            load[m] += bsum[order[i]];
-            W.bthread[order[i]] = (uint8_t)m;
-        }
-    }
+    place_buckets(W, nth);
 
     const Huff h{dec, out_off, len, st, lbase.data()};
     std::vector<int> wait_rc(nth, 0);
@@ -875,35 +1046,7 @@ extern "C" int hpk_hdec_decode_blocks(hpk_ctx* ctx, hpk_hdec* const* decs, const
     }
     const long us_apply = us(t_2);
     auto t_3 = now();
-    // join the per-thread outputs into the caller's buffers
-    std::vector<uint32_t>&abase = W.abase, &hbase = W.hbase;
-    abase.assign(nth, 0);
-    hbase.assign(nth, 0);
-    size_t at = 0, ht = 0;
-    for (int t = 0; t < nth; ++t) {
-        abase[t] = (uint32_t)at;
-        hbase[t] = (uint32_t)ht;
-        at += outs[t].an;
-        ht += outs[t].hn;
-    }
-    out->arena_len = at;
-    out->n_headers = ht;
-    out->arena = (uint8_t*)g_out_cache.take(0, at);
-    out->headers = (hpk_header*)g_out_cache.take(1, ht * sizeof(hpk_header));
-    if (at >= (1ull << 32) || !out->arena || !out->headers) {
-        hpk_blocks_out_free(out);
-        return HPK_E_INVAL;
-    }
-    parallel([&](int t) {
-        if (outs[t].an) memcpy(out->arena + abase[t], outs[t].arena.data(), outs[t].an);
-        for (size_t j = 0; j < outs[t].hn; ++j) {
-            hpk_header hd = outs[t].headers[j];
-            hd.name_off += abase[t];
-            hd.value_off += abase[t];
-            out->headers[hbase[t] + j] = hd;
-        }
-        for (uint32_t b = blk0(t); b < blk0(t + 1); ++b) res[b].first_header += hbase[owner[b]];
-    });
+    if (int jrc = join_outputs(W, nth, nblocks, out, parallel)) return jrc;
     if (timing)
         fprintf(stderr, "hpk_hdec_decode_blocks: %d threads, scan %ld us, batch %s %ld us, apply %ld us, join %ld us\n",
                 nth, us_scan, ctx ? "issue" : "cpu", us_batch, us_apply, us(t_3));
