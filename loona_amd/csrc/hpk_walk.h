@@ -450,6 +450,20 @@ __device__ __forceinline__ void tail12_begin(Tail12& T, const Lit12& L) {
     T.o = L.o;
 }
 
+// The tail's state word alone, made where the lane still holds its dword pair (the wave kernel saves it when a
+// lane's first literal leaves its body, fill trim A): Tail12::n as tail12_begin makes it from the same state.
+// rem = Eb - X <= 30 there (0 after a status in the body, or in an empty slot: the word is then 0).
+__device__ __forceinline__ uint32_t tail12_word(const Lit12& L) {
+    return ~__builtin_amdgcn_alignbit(L.d0, L.d1, ~L.X) & ~(0xFFFFFFFFu >> (L.Eb - L.X));
+}
+// tail12_begin from a saved word: no dword of the window is needed (nor loaded) for the masked tail
+__device__ __forceinline__ void tail12_begin_saved(Tail12& T, uint32_t n, uint32_t rem, uint32_t o) {
+    T.rem = rem;
+    T.n = n;
+    T.used = 0;
+    T.o = o;
+}
+
 template <int kStore, int kTab>
 __device__ __forceinline__ void tail12_look(Tail12& T, const uint32_t* __restrict__ lut, uint8_t* __restrict__ out8,
                                             uint32_t dmy) {

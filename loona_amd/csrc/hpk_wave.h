@@ -77,8 +77,19 @@
 #ifndef HPK_PF_EARLY
 #define HPK_PF_EARLY 1  // 1 (v40): the next fill's loads issued ahead of the write-back's stores; 0: behind them (v39)
 #endif
+// Fill trim (v42): work around the lane loop that the result does not need, each part on its own switch.
+#ifndef HPK_TAIL_SAVED
+#define HPK_TAIL_SAVED 1  // 1: the first literal's masked tail starts from the state word saved when its body ended
+                          // (tail12_word: one register beside aX, aO, aSt), and only the tail's slow lanes reload
+                          // their window dwords; 0: every lane reloads three dwords before the tails (v38)
+#endif
+#ifndef HPK_ST_CARRY
+#define HPK_ST_CARRY 1  // 1: the first slot's status is the one its tail computed (tail12_end), the tail's slow lanes
+                        // taking theirs from their dword pair behind one wave-uniform test; 0: every lane re-reads the
+                        // window at its stop (win_at, two LDS reads) and computes the residual status again
+#endif
 #ifndef HPK_WIN_CUT
-#define HPK_WIN_CUT 1  // 1: the window loads stop at the literal chunk's last input byte (round 6: config-5
+#define HPK_WIN_CUT 1 // 1: the window loads stop at the literal chunk's last input byte (round 6: config-5
                        // reads 1.229 -> 1.178 GB per launch, time unchanged)
 #endif
 
@@ -874,6 +885,10 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 bool body = L.Eb - L.X >= body_min<kTab>();
                 uint32_t aX = L.X, aO = L.o, aSt = L.st;
                 bool aAct = L.act, onA = true;
+                // (every lane switches exactly once before the loop ends, a lane with no second literal to an
+                // empty slot: the loop ends when no lane is in a body, and a lane not in a body switches first)
+                constexpr bool kSaved = HPK_TAIL_SAVED != 0 && HPK_TAIL_MASKED != 0, kCarry = HPK_ST_CARRY != 0;
+                uint32_t aN = 0;  // kSaved: the first literal's tail word (Tail12::n), made from its dword pair
                 for (;;) {
                     dg_add(9, 1u);
                     if (kRound)  // v41: the round's steps nested, one narrowing of exec each (lit12_round)
@@ -904,6 +919,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                             aO = L.o;
                             aSt = L.st;
                             aAct = L.act;
+                            if (kSaved) aN = tail12_word(L);
                             load(L, e2, t2);
                             onA = false;
                             body = L.Eb - L.X >= body_min<kTab>();
@@ -923,29 +939,46 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 L.o0 = obase + ((e1.y >> 12) & 0x1FFFFu);
                 L.idx = e1.y & 0xFFFu;
                 if (aSt != HPK_OK) L.Eb = L.X;  // ended in its body (EOS / padding): no tail
-                lit12_load(L, wl32);
+                if (!kSaved) lit12_load(L, wl32);
                 L.more = L.Eb - L.X >= 5u;  // (fewer bits than the shortest code: ended)
                 N.more = N.Eb - N.X >= 5u;
                 stamp(12);
+                bool slowL = true;  // the first literal's walk did not end in the masked tail
                 if (HPK_TAIL_MASKED) {
                     // v38: the masked tail (lit12_tail) on both literals, the two chains' lookups in turn
                     // (they are independent and neither waits); a lane it leaves as slow (a 13..28-bit
                     // code in the tail, or a code cut by the literal's end) keeps its state and takes the
                     // checked steps below, the other lanes' walks have ended
                     Tail12 TL, TN;
-                    tail12_begin(TL, L);
+                    if (kSaved)
+                        tail12_begin_saved(TL, aN, L.Eb - L.X, L.o);
+                    else
+                        tail12_begin(TL, L);
                     tail12_begin(TN, N);
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         tail12_look<kStore, kTab>(TL, s_lut, ol8, dmy);
                         tail12_look<kStore, kTab>(TN, s_lut, ol8, dmy);
                     }
-                    L.more &= tail12_end<kTab>(TL, L);
+                    slowL = tail12_end<kTab>(TL, L);
+                    L.more &= slowL;
                     N.more &= tail12_end<kTab>(TN, N);
+                }
+                // a slow first literal (a 14..30-bit code in its tail, a code cut by its end, or residual bits
+                // that complete a code with the ones past the end: 2.7 % of config 5's fills hold one) takes
+                // its dwords now, for the checked steps and for its status
+                if (kSaved && __any(slowL)) {
+                    if (slowL) lit12_load(L, wl32);
                 }
                 while (__any(L.more | N.more)) {
                     if (L.more) lit12_step<kStore, true, kTab, true>(L, wl32, s_lut, s_lo, ol8, dmy);
                     if (N.more) lit12_step<kStore, true, kTab, true>(N, wl32, s_lut, s_lo, ol8, dmy);
+                }
+                // kCarry: every other lane's st is already final (tail12_end: the residual bits' status unless
+                // the body set one); a slow lane's comes from the window at its stop (from its dword pair, as the
+                // second slot's: 8 bytes of scratch in the region instantiation)
+                if (kCarry && __any(slowL)) {
+                    if (slowL && L.st == HPK_OK) L.st = residual_status(L.Eb - L.X, win_at(wl32, L.X - 31u));
                 }
                 // results: the first slot's end state saved, the second in L
                 sX = L.X;
@@ -961,7 +994,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
             // results: the first slot's from its saved end state, the second's from the walk
             {
                 const uint32_t Eb = wbits + (e1.x & 0xFFFFu) * 8u + 31u + (e1.x >> 16) * 8u;
-                const uint32_t st = sSt != HPK_OK ? sSt : residual_status(Eb - sX, win_at(wl32, sX - 31u));
+                const uint32_t st = HPK_ST_CARRY != 0 || sSt != HPK_OK ? sSt : residual_status(Eb - sX, win_at(wl32, sX - 31u));
                 rv0 = (sO - obase - ((e1.y >> 12) & 0x1FFFFu)) | (st << 24);
                 ri0 = s1 ? e1.y & 0xFFFu : 0xFFFFFFFFu;
                 rv1 = (Lend - L.o0) | (lit12_status(L) << 24);
