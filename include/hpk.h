@@ -496,6 +496,99 @@ int hpk_scan_blocks(hpk_ctx* ctx, const uint8_t* blocks, size_t cap, const uint3
 #define HPK_BLOCK_SCAN_DEVICE 1
 int hpk_ctx_set_block_scan(hpk_ctx* ctx, int kind);
 
+/* ---- HPACK header blocks: the apply on the device ------------------------------------------
+ * hpk_apply_blocks applies the field records of many header blocks, in order, against each connection's dynamic
+ * table: the batch form of the table-dependent half of Decoder::decode_with_cb (crates/loona-hpack/src/decoder.rs:
+ * 368-450: the indexed lookup :387-392, the literals :393-430 with decode_literal :502-527, update_max_dynamic_size
+ * :537-554, SizeUpdateAtEnd :445-447) and of the table itself (crates/loona-hpack/
+ * src/lib.rs: DynamicTable :43-164 with add_header :108-122 and consolidate_table :124-142, get_from_table :228-255),
+ * the counterpart of the table-free half that hpk_scan_blocks covers. Its inputs are hpk_scan_blocks' fields and
+ * field_off and, for the scan's string list, hpk_decode_strings_packed's out_off / out_len / status.
+ * The arena. The apply never touches a byte of any string: names and values are references. Every offset is a u32
+ * into ONE arena that the caller defines and the call never reads: the static text (hpk_static_table) lies at
+ * static_base, string s of the list at str_base + str_out_off[s], and the entries of the tables carried in wherever
+ * the caller's tab_ent records say. An emitted header is an hpk_header whose offsets point into that arena, and so
+ * is an entry of a table that comes back. static_base + the static text's length must not pass 2^32 (HPK_E_INVAL).
+ * Decoders. Decoder d applies blocks dec_blk[dec_blk_off[d] .. dec_blk_off[d+1]) in that order (a connection's
+ * blocks in connection order; the lists of different decoders may interleave in any way, and a block belongs to at
+ * most one list) against tabs[d]: its entries are tab_ent[ent .. ent + count), newest first, of cap records it may
+ * grow into. count, size and max_size come back updated with the entries in the same layout.
+ * Results. results[b] is exactly what hpk_hdec_decode_blocks gives for block b on the same state: n_headers before
+ * the first error, error and detail with the reference's precedence; first_header = field_off[b], block b's headers
+ * are headers[field_off[b] .. field_off[b] + n_headers) (a field emits at most one header, so the field total is the
+ * capacity that always suffices and there is no count pass), and records of headers that no block covers are not
+ * written. results of a block in no list is zero. ndecs == 0 or nblocks == 0 does nothing but zero results.
+ * Deferral. On the device a decoder's table is a ring of ring_entries records (hpk_test_blkapply_geometry). With
+ * lim = min(ring_entries, tabs[d].cap), a block is deferred, before it touches the table, when the decoder's
+ * max_size at the call's start exceeds 32 * lim (or its count exceeds lim), or when any size update record of the
+ * block carries a value above 32 * lim. Every later block of the list is deferred too: result HPK_BLK_DEFERRED with
+ * 0 headers, tabs[d] as it was after the last applied block, and tabs[d].applied the number of blocks applied: where
+ * the caller takes over (hpk_hdec_decode_blocks applies them on the host). An entry takes at least 32 octets of the
+ * size, so the live count never passes lim otherwise.
+ * Bad inputs (the rule for device pointers, as hpk_decode_batch). A decoder is void when its ent + cap passes
+ * tab_ent_cap or its count its cap; when its list's offsets decrease or pass dec_blk_off[ndecs]; when a listed block
+ * index is >= nblocks; when a listed block's field_off decreases or passes headers_cap (fields and headers are
+ * arrays of headers_cap records); when a field's str + nstr passes nstrs; or when str_base + out_off + out_len of a
+ * listed string passes 2^32. All blocks of a void decoder are HPK_BLK_DEFERRED, its applied is 0 and its table
+ * untouched; the sticky flag is set (a synchronous call then returns HPK_E_INVAL). Nothing outside the arrays'
+ * stated sizes is read or written. If field_off[nblocks] > headers_cap a synchronous call returns HPK_E_NOSPACE
+ * (HPK_E_INVAL wins over it); after HPK_ASYNC the caller compares.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC (anything else is HPK_E_INVAL); fields, headers and tab_ent must be
+ * 16-byte aligned (HPK_E_INVAL). On the context's stream; no scratch; always the launch path: the small-call mode
+ * does not answer it.
+ * How: one kernel, one wave per decoder (hpk_blkapply.hip). A lane-parallel look over the decoder's records finds
+ * the bad inputs and the deferring size updates; then per chunk of chunk_fields records the lanes stage everything
+ * that does not depend on the table (one 16-byte load each and the strings' three arrays), the wave resolves the
+ * records in order against the ring in LDS, and the chunk's headers go out as one 16-byte store per lane. */
+typedef struct hpk_dtab {   /* one decoder's dynamic table for hpk_apply_blocks; 32 bytes */
+    uint32_t ent, cap;      /* its entries are tab_ent[ent .. ent + cap); entries 0 .. count-1, newest first */
+    uint32_t count, size;   /* in/out: entries, and the RFC 7541 §4.1 size (sum of name + value + 32) */
+    uint32_t max_size;      /* in/out: the current limit (SizeUpdate changes it) */
+    uint32_t max_allowed;   /* in: the SETTINGS limit (decoder.rs:316-318), HPK_DTAB_NO_LIMIT = none set */
+    uint32_t applied;       /* out: how many blocks of this decoder's list were applied (the rest are deferred) */
+    uint32_t reserved;
+} hpk_dtab;
+#define HPK_DTAB_NO_LIMIT 0xFFFFFFFFu
+#define HPK_BLK_DEFERRED 10 /* hpk_block_result.error, hpk_apply_blocks only: not applied, the decoder untouched from here on */
+
+int hpk_apply_blocks(hpk_ctx* ctx,
+        const hpk_field* fields, const uint32_t* field_off, uint32_t nblocks,        /* hpk_scan_blocks' outputs */
+        const uint32_t* str_out_off, const uint32_t* str_out_len, const uint8_t* str_status, uint32_t nstrs,
+                                                               /* hpk_decode_strings_packed's, for the scan's string list */
+        uint32_t str_base, uint32_t static_base,               /* where the packed strings / the static text lie in the arena */
+        const uint32_t* dec_blk_off, const uint32_t* dec_blk, uint32_t ndecs,
+                                  /* decoder d's blocks, in connection order: dec_blk[dec_blk_off[d] .. dec_blk_off[d+1]) */
+        hpk_dtab* tabs, hpk_header* tab_ent, size_t tab_ent_cap,
+        hpk_header* headers, size_t headers_cap, hpk_block_result* results, int flags);
+
+/* RFC 7541 App. A as the kernel sees it (the reference's STATIC_TABLE, crates/loona-hpack/src/lib.rs:293-356): the
+   61 entries' names and values end to end, and 61 hpk_header records with offsets relative to the text's start.
+   Host memory of the library, valid for the process. Any of the three pointers may be NULL. */
+int hpk_static_table(const uint8_t** text, size_t* text_len, const hpk_header** entries);
+
+/* Where hpk_hdec_decode_blocks (and hpk_h2_read_frames, which calls it) applies a context's blocks.
+ * HPK_BLOCK_APPLY_HOST (the default): on the host, after the scan hpk_ctx_set_block_scan selects.
+ * HPK_BLOCK_APPLY_DEVICE (opt-in; calls without a context are not affected) selects the whole device pipeline,
+ * whatever hpk_ctx_set_block_scan says: the blocks are grouped by decoder on the host; every distinct decoder's live
+ * entries and their bytes go up with the blocks as hpk_dtab / hpk_header records and a blob of prior bytes; the
+ * device-scan path's steps run as they are (count, scans, totals, emit, strings); hpk_apply_blocks' kernel applies;
+ * results and tabs come back. If no block was deferred, the header records, the tables' final entries and exactly
+ * the packed bytes come back: out->arena is the static text, then the prior bytes, then the packed strings;
+ * out->headers is the field-total array (out->n_headers its length, first_header = field_off[b], records that no
+ * block covers zero); and every decoder's table is rebuilt from its final entries' bytes in that arena. If any
+ * block was deferred (or a decoder's max_size exceeds 32 * ring_entries, or its count ring_entries, before the call,
+ * which the host sees without the device), the field records come back instead and the device-scan path's host apply
+ * runs for the whole call: no decoder has been touched until then, so nothing is merged. Results and decoder states
+ * equal the default path's exactly. Nothing is written to a decoder before everything is back, so a device failure on
+ * this path leaves every decoder untouched. */
+#define HPK_BLOCK_APPLY_HOST 0    /* the default */
+#define HPK_BLOCK_APPLY_DEVICE 1
+int hpk_ctx_set_block_apply(hpk_ctx* ctx, int kind);
+/* Testing only: the block apply's geometry (hpk_apply_blocks): the records of a decoder's ring in LDS, the field
+ * records a wave stages at a time, and the decoders per workgroup (one wave each). The tests place their cases
+ * relative to these. */
+int hpk_test_blkapply_geometry(uint32_t* ring_entries, uint32_t* chunk_fields, uint32_t* wg_decoders);
+
 /* ---- HTTP/2 framing in front of the block decoder ------------------------
  * hpk_h2conn is one connection's header-reading state: its HPACK decoder and a HEADERS block still
  * waiting for CONTINUATION frames. hpk_h2_read_frames takes the bytes received on many

@@ -41,6 +41,13 @@ HPK_MAX_OFFSET = 0xFFFFFFDF  # offsets of one shard stay at or below this (hpk.h
 HPK_BLOCK_SCAN_HOST = 0
 HPK_BLOCK_SCAN_DEVICE = 1
 
+# hpk_ctx_set_block_apply (hpk.h)
+HPK_BLOCK_APPLY_HOST = 0
+HPK_BLOCK_APPLY_DEVICE = 1
+# hpk_apply_blocks (hpk.h)
+HPK_DTAB_NO_LIMIT = 0xFFFFFFFF
+HPK_BLK_DEFERRED = 10
+
 # string-literal policies of hpk_encode_strings_packed (hpk.h)
 HPK_STR_AUTO = 0
 HPK_STR_RAW = 1
@@ -73,6 +80,10 @@ EXPORTS = (
     "hpk_decode_strings_packed",
     "hpk_scan_blocks",
     "hpk_ctx_set_block_scan",
+    "hpk_apply_blocks",
+    "hpk_static_table",
+    "hpk_ctx_set_block_apply",
+    "hpk_test_blkapply_geometry",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -222,6 +233,19 @@ def lib() -> ctypes.CDLL:
             L.hpk_scan_blocks.restype = ctypes.c_int
             L.hpk_ctx_set_block_scan.argtypes = [ctypes.c_void_p, ctypes.c_int]
             L.hpk_ctx_set_block_scan.restype = ctypes.c_int
+        if hasattr(L, "hpk_apply_blocks"):  # (likewise: no block apply)
+            L.hpk_apply_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.c_void_p, ctypes.c_int]
+            L.hpk_apply_blocks.restype = ctypes.c_int
+            L.hpk_static_table.argtypes = [ctypes.POINTER(ctypes.c_void_p), c_sizep, ctypes.POINTER(ctypes.c_void_p)]
+            L.hpk_static_table.restype = ctypes.c_int
+            L.hpk_ctx_set_block_apply.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.hpk_ctx_set_block_apply.restype = ctypes.c_int
+            L.hpk_test_blkapply_geometry.argtypes = [c_u32p] * 3
+            L.hpk_test_blkapply_geometry.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -22,6 +22,11 @@ import numpy as np
 from . import _lib
 
 U32 = np.uint32
+# hpk_header, hpk_block_result and hpk_dtab (hpk.h), for apply_blocks' byte tensors
+HEADER_DTYPE = np.dtype([("name_off", "<u4"), ("name_len", "<u4"), ("value_off", "<u4"), ("value_len", "<u4")])
+RESULT_DTYPE = np.dtype([("first_header", "<u4"), ("n_headers", "<u4"), ("error", "<i4"), ("detail", "<i4")])
+DTAB_DTYPE = np.dtype([("ent", "<u4"), ("cap", "<u4"), ("count", "<u4"), ("size", "<u4"), ("max_size", "<u4"),
+                       ("max_allowed", "<u4"), ("applied", "<u4"), ("reserved", "<u4")])
 # hpk_field (hpk.h): one 16-byte record of scan_blocks
 FIELD_DTYPE = np.dtype([("index", "<u4"), ("str", "<u4"), ("kind", "u1"), ("nstr", "u1"), ("err", "u1"),
                         ("err_stage", "u1"), ("at", "<u4")])
@@ -699,6 +704,71 @@ class HuffmanCodec:
         self._scan_blocks_call(blocks, block_off, fields, field_off, str_off, str_end, str_blk_off, status, False, True)
         nf, ns = int(field_off[n]), int(str_blk_off[n])
         return fields[: 16 * nf].view(FIELD_DTYPE), field_off, str_off[:ns], str_end[:ns], str_blk_off, status[:n]
+
+    BLOCK_APPLIES = {"host": _lib.HPK_BLOCK_APPLY_HOST, "device": _lib.HPK_BLOCK_APPLY_DEVICE}
+
+    def set_block_apply(self, kind: str):
+        """'host' (the default) or 'device' (hpk_ctx_set_block_apply): where hpack.decode_blocks and
+        h2.read_frames apply this codec's header blocks against the decoders' tables. 'device' selects the whole
+        device pipeline whatever set_block_scan says: scan_blocks' kernels, decode_strings' pipeline and
+        apply_blocks' kernel, the tables carried to the device and back. The same results and decoder states."""
+        if kind not in self.BLOCK_APPLIES:
+            raise ValueError(f"block apply {kind!r} not in {tuple(self.BLOCK_APPLIES)}")
+        _lib.check(self._L.hpk_ctx_set_block_apply(self._h, self.BLOCK_APPLIES[kind]), "hpk_ctx_set_block_apply")
+
+    def apply_blocks(self, fields, field_off, str_out_off, str_out_len, str_status, nstrs, str_base, static_base, dec_blk_off,
+                     dec_blk, tabs, tab_ent, headers=None, results=None, sync=False):
+        """hpk_apply_blocks: torch cuda tensors -> (headers, results); tabs and tab_ent are updated in place.
+        fields / field_off are scan_blocks' outputs, str_out_off / str_out_len / str_status decode_strings' for the
+        scan's string list (nstrs of them). Every offset is into one arena the caller defines and the call never
+        reads: the static text (static_table()) at static_base, string s at str_base + str_out_off[s], the
+        carried-in table entries wherever tab_ent says. Decoder d applies blocks dec_blk[dec_blk_off[d] :
+        dec_blk_off[d + 1]] in order against tabs[d] (a uint8 tensor of 32-byte hpk_dtab records: view it with
+        DTAB_DTYPE on the host), whose entries are the 16-byte hpk_header records tab_ent[ent : ent + count],
+        newest first (tab_ent: a uint8 tensor, HEADER_DTYPE). headers (uint8, 16 bytes per record; capacity
+        headers.numel() // 16, by default fields' record count) gets block b's headers at records field_off[b] ..
+        field_off[b] + n_headers; results (uint8, 16 bytes per block, RESULT_DTYPE) the blocks' first_header,
+        n_headers, error and detail. error 10 (HPK_BLK_DEFERRED): the block was not applied, tabs[d]['applied'] says
+        how many of the decoder's list were. With sync=True bad inputs raise (HPK_E_INVAL), and so does a field total
+        above the headers' capacity (HPK_E_NOSPACE)."""
+        import torch
+
+        dev = self.device
+        n = int(field_off.shape[0]) - 1
+        nd = int(dec_blk_off.shape[0]) - 1
+        if n < 0 or nd < 0:
+            raise ValueError("field_off and dec_blk_off need n+1 >= 1 entries")
+        if headers is None:
+            headers = torch.empty(max(int(fields.numel()), 16), dtype=torch.uint8, device=fields.device)[: int(fields.numel())]
+        if results is None:
+            results = torch.empty(16 * max(n, 1), dtype=torch.uint8, device=fields.device)
+        pf, fbytes = _arg(fields, "fields", ("uint8",), 0, dev)
+        pfo, _ = _arg(field_off, "field_off", _OFF_DTYPES, n + 1, dev)
+        poo, _ = _arg(str_out_off, "str_out_off", _OFF_DTYPES, nstrs, dev)
+        pol, _ = _arg(str_out_len, "str_out_len", _OFF_DTYPES, nstrs, dev)
+        pst, _ = _arg(str_status, "str_status", ("uint8",), nstrs, dev)
+        pdo, _ = _arg(dec_blk_off, "dec_blk_off", _OFF_DTYPES, nd + 1, dev)
+        pdb, _ = _arg(dec_blk, "dec_blk", _OFF_DTYPES, 0, dev)
+        pt, tbytes = _arg(tabs, "tabs", ("uint8",), 32 * nd, dev)
+        pe, ebytes = _arg(tab_ent, "tab_ent", ("uint8",), 0, dev)
+        ph, hbytes = _arg(headers, "headers", ("uint8",), 0, dev)
+        pr, _ = _arg(results, "results", ("uint8",), 16 * n, dev)
+        self._follow()
+        flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        rc = self._L.hpk_apply_blocks(self._h, pf, pfo, ctypes.c_uint32(n), poo, pol, pst, ctypes.c_uint32(int(nstrs)),
+                                      ctypes.c_uint32(int(str_base)), ctypes.c_uint32(int(static_base)), pdo, pdb,
+                                      ctypes.c_uint32(nd), pt, pe, ebytes // 16, ph, hbytes // 16, pr, flags)
+        _lib.check(rc, "hpk_apply_blocks")
+        return headers, results
+
+
+def static_table():
+    """hpk_static_table: RFC 7541 App. A as apply_blocks' kernel sees it -> (text, entries): the 61 names and
+    values end to end (bytes) and a HEADER_DTYPE array of 61 records with offsets relative to the text."""
+    L = _lib.lib()
+    text, ent, ln = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+    _lib.check(L.hpk_static_table(ctypes.byref(text), ctypes.byref(ln), ctypes.byref(ent)), "hpk_static_table")
+    return ctypes.string_at(text.value, ln.value), np.frombuffer(ctypes.string_at(ent.value, 61 * 16), dtype=HEADER_DTYPE).copy()
 
 
 def _bound_offsets_torch(in_off, num, den, add):

@@ -8,7 +8,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.44 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block)"
+#define HPK_VERSION "hpk 0.45 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block); block apply v1 (one wave per decoder: lane-parallel look and stage, records resolved in order against a ring in LDS)"
 
 static thread_local std::string t_last_error;
 
@@ -166,6 +166,7 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     (void)hipFree(c->d_lut13);
     (void)hipFree(c->d_lo);
     (void)hipFree(c->d_codes);
+    (void)hipFree(c->d_static);
     (void)hipFree(c->d_in);
     (void)hipFree(c->d_out);
     (void)hipFree(c->d_meta);
@@ -175,7 +176,7 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     for (hpk_slot& s : c->slots) {
         if (s.ev_set) (void)hipEventSynchronize(s.ev);
         for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage, &s.sd_meta,
-                          &s.sd_hblob, &s.sd_stage, &s.bs_meta, &s.bs_stage, &s.bs_out})
+                          &s.sd_hblob, &s.sd_stage, &s.bs_meta, &s.bs_stage, &s.bs_out, &s.ba_buf})
             (void)hipFree(b->p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
@@ -243,6 +244,14 @@ extern "C" int hpk_ctx_set_block_scan(hpk_ctx* c, int kind) {
 }
 
 int hpk_ctx_block_scan(const hpk_ctx* c) { return c ? c->block_scan : HPK_BLOCK_SCAN_HOST; }
+
+extern "C" int hpk_ctx_set_block_apply(hpk_ctx* c, int kind) {
+    if (!c || (kind != HPK_BLOCK_APPLY_HOST && kind != HPK_BLOCK_APPLY_DEVICE)) return hpk_set_err_msg("bad block apply", HPK_E_INVAL);
+    c->block_apply = kind;
+    return HPK_E_OK;
+}
+
+int hpk_ctx_block_apply(const hpk_ctx* c) { return c ? c->block_apply : HPK_BLOCK_APPLY_HOST; }
 
 extern "C" void* hpk_ctx_stream(hpk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
@@ -1022,13 +1031,63 @@ extern "C" int hpk_scan_blocks(hpk_ctx* c, const uint8_t* blocks, size_t cap, co
     return blkscan_end(c, field_off + nblocks, fields_cap, str_blk_off + nblocks, strs_cap, flags);
 }
 
+// The static records in device memory, uploaded once per context.
+static int apply_static(hpk_ctx* c) {
+    if (c->d_static) return HPK_E_OK;
+    const hpk_header* ent = nullptr;
+    (void)hpk_static_table(nullptr, nullptr, &ent);
+    hpk_header* d = nullptr;
+    HIP_TRY(hipMalloc(&d, 61 * sizeof(hpk_header)));
+    const hipError_t e = hipMemcpy(d, ent, 61 * sizeof(hpk_header), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hpk_set_err("upload the static table", e);
+    }
+    c->d_static = d;
+    return HPK_E_OK;
+}
+
+// The header-block apply (include/hpk.h).
+extern "C" int hpk_apply_blocks(hpk_ctx* c, const hpk_field* fields, const uint32_t* field_off, uint32_t nblocks,
+                                const uint32_t* str_out_off, const uint32_t* str_out_len, const uint8_t* str_status, uint32_t nstrs,
+                                uint32_t str_base, uint32_t static_base, const uint32_t* dec_blk_off, const uint32_t* dec_blk,
+                                uint32_t ndecs, hpk_dtab* tabs, hpk_header* tab_ent, size_t tab_ent_cap, hpk_header* headers,
+                                size_t headers_cap, hpk_block_result* results, int flags) {
+    if (!c || (nblocks && !results)) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the block apply takes device pointers only", HPK_E_INVAL);
+    if (nblocks >= 0x7FFFFFFFu || ndecs >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the block apply", HPK_E_INVAL);
+    if ((((uintptr_t)fields | (uintptr_t)headers | (uintptr_t)tab_ent) & 15u) != 0)
+        return hpk_set_err_msg("fields, headers and tab_ent must be 16-byte aligned", HPK_E_INVAL);
+    size_t static_len = 0;
+    (void)hpk_static_table(nullptr, &static_len, nullptr);
+    if ((uint64_t)static_base + static_len > (1ull << 32)) return hpk_set_err_msg("the static text would pass 2^32", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (nblocks) HIP_TRY(hipMemsetAsync(results, 0, (size_t)nblocks * sizeof(hpk_block_result), c->stream));
+    if (ndecs == 0 || nblocks == 0) return call_end(c, flags);
+    if (!field_off || !dec_blk_off || !dec_blk || !tabs || (headers_cap && (!fields || !headers)) || (tab_ent_cap && !tab_ent) ||
+        (nstrs && (!str_out_off || !str_out_len || !str_status)))
+        return hpk_set_err_msg("null array", HPK_E_INVAL);
+    if (int rc = apply_static(c)) return rc;
+    if (int rc = hpk_launch_blkapply(c, fields, field_off, nblocks, str_out_off, str_out_len, str_status, nstrs, str_base, static_base,
+                                     dec_blk_off, dec_blk, ndecs, tabs, tab_ent, tab_ent_cap, headers, clamp_u32(headers_cap),
+                                     results, c->d_static))
+        return rc;
+    if (flags & HPK_ASYNC) return HPK_E_OK;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, field_off + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = call_end(c, flags)) return rc;
+    if ((size_t)total > headers_cap) return hpk_set_err_msg("the field total passes headers_cap", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
 // The block decoder's device-scan path (hpk_hpack.cpp, HPK_BLOCK_SCAN_DEVICE; not in the C ABI): block_off is
 // non-decreasing (the caller's check). The blocks and block_off go up once as they are; the count pass and the
 // scans run and the two totals come back (the pipeline's one wait before its end); the outputs are sized by them;
 // the emit pass and hpk_decode_strings_packed's steps over every listed string follow; then the field records,
 // field_off and the strings' out_off / out_len / status come back into the context's page-locked area, and with
 // out_off's last entry known, exactly the packed bytes. Everything is on the host when this returns HPK_E_OK.
-int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o) {
+int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o,
+                      hpk_applyplan* plan) {
     *o = hpk_blkdev{};
     if (nblocks == 0) return HPK_E_OK;
     if (nblocks >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the block scan", HPK_E_INVAL);
@@ -1084,8 +1143,65 @@ int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_o
         return rc;
     // back into the page-locked area: fields | field_off | out_off | out_len | status | the packed bytes
     const size_t h_foff = 16 * (size_t)nf, h_oo = h_foff + offs, h_ol = h_oo + sw, h_ss = h_ol + sw, h_out = h_ss + up16(ns);
+    // (with a plan, behind them: results | tabs | headers | the tables' entries)
+    const size_t nd = plan ? plan->ndecs : 0, ne = plan ? plan->nent : 0;
+    const size_t h_res = up16(h_out + dcap + 16), h_tabs = h_res + 16 * (size_t)nblocks, h_hdr = h_tabs + 32 * nd;
+    const size_t h_ent = h_hdr + 16 * (size_t)nf;
     uint8_t* h = nullptr;
-    if ((rc = hpk_ctx_pinned(c, h_out + dcap + 16, (void**)&h))) return rc;
+    if ((rc = hpk_ctx_pinned(c, plan ? h_ent + 16 * ne + 16 : h_out + dcap + 16, (void**)&h))) return rc;
+    if (plan) {
+        // HPK_BLOCK_APPLY_DEVICE: the lists and the tables go up, hpk_apply_blocks' kernel runs on what the steps
+        // above left on the device, and the results, the tables' records and the strings' total come back. Nothing
+        // deferred: the header records, the tables' entries and exactly the packed bytes follow, and the field
+        // records and the strings' arrays stay where they are. Else the call goes on as without a plan.
+        const auto t_a = now();
+        plan->applied = 0;
+        const size_t a_off = up16(4 * (nd + 1)), a_blk = up16(4 * (size_t)nblocks);
+        const size_t at_blk = a_off, at_tabs = at_blk + a_blk, at_ent = at_tabs + 32 * nd, at_res = at_ent + 16 * ne;
+        const size_t at_hdr = at_res + 16 * (size_t)nblocks;
+        if ((rc = slot_reserve(c, s, {{&s->ba_buf, at_hdr + 16 * (size_t)nf + 16}})) || (rc = apply_static(c))) return rc;
+        uint8_t* a = s->ba_buf.as<uint8_t>();
+        HIP_TRY(hipMemcpyAsync(a, plan->dec_blk_off, 4 * (nd + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(a + at_blk, plan->dec_blk, 4 * (size_t)nblocks, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(a + at_tabs, plan->tabs, 32 * nd, hipMemcpyHostToDevice, c->stream));
+        if (ne) HIP_TRY(hipMemcpyAsync(a + at_ent, plan->tab_ent, 16 * ne, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(a + at_res, 0, 16 * ((size_t)nblocks + nf), c->stream));  // the results and the header records
+        if ((rc = hpk_launch_blkapply(c, d_fields, d_foff, nblocks, d_oo, d_ol, q + at_ss, ns, plan->str_base, 0u,
+                                      reinterpret_cast<uint32_t*>(a), reinterpret_cast<uint32_t*>(a + at_blk), plan->ndecs,
+                                      reinterpret_cast<hpk_dtab*>(a + at_tabs), reinterpret_cast<hpk_header*>(a + at_ent), ne,
+                                      reinterpret_cast<hpk_header*>(a + at_hdr), nf,
+                                      reinterpret_cast<hpk_block_result*>(a + at_res), c->d_static)))
+            return rc;
+        uint32_t total = 0;
+        HIP_TRY(hipMemcpyAsync(h + h_res, a + at_res, 16 * (size_t)nblocks, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h + h_tabs, a + at_tabs, 32 * nd, hipMemcpyDeviceToHost, c->stream));
+        if (ns) HIP_TRY(hipMemcpyAsync(&total, d_oo + ns, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((rc = take_err(c))) return rc;  // (a void decoder: the lists or the tables the host made are wrong)
+        const hpk_dtab* tb = reinterpret_cast<const hpk_dtab*>(h + h_tabs);
+        bool deferred = false;
+        for (size_t k = 0; k < nd; ++k) deferred |= tb[k].applied != plan->dec_blk_off[k + 1] - plan->dec_blk_off[k];
+        plan->us_apply = us(t_a);
+        if (!deferred) {
+            if (total > dcap) return hpk_set_err_msg("the blocks' strings pass their decoded bound", HPK_E_DEVICE);
+            if (nf) HIP_TRY(hipMemcpyAsync(h + h_hdr, a + at_hdr, 16 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+            if (ne) HIP_TRY(hipMemcpyAsync(h + h_ent, a + at_ent, 16 * ne, hipMemcpyDeviceToHost, c->stream));
+            if (total) HIP_TRY(hipMemcpyAsync(h + h_out, q + at_out, total, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if ((rc = slot_commit(c, s))) return rc;
+            plan->applied = 1;
+            plan->results = reinterpret_cast<const hpk_block_result*>(h + h_res);
+            plan->tabs_out = tb;
+            plan->headers = reinterpret_cast<const hpk_header*>(h + h_hdr);
+            plan->ent_out = reinterpret_cast<const hpk_header*>(h + h_ent);
+            plan->packed_len = total;
+            o->arena = h + h_out;
+            o->nfields = nf;
+            o->nstrs = ns;
+            o->us_strings = us(t_1);
+            return HPK_E_OK;
+        }
+    }
     if (nf) HIP_TRY(hipMemcpyAsync(h, d_fields, 16 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(h + h_foff, d_foff, 4 * ((size_t)nblocks + 1), hipMemcpyDeviceToHost, c->stream));
     uint32_t* h_off = reinterpret_cast<uint32_t*>(h + h_oo);

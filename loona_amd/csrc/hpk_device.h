@@ -65,6 +65,8 @@ struct hpk_slot {
     // the header-block scan (hpk_scan_blocks): the count pass's two arrays; the staged input and arrays of its host
     // form and of the block decoder's device-scan path; and that path's outputs, sized once the totals are known
     DevBuf bs_meta, bs_stage, bs_out;
+    // the block decoder's device-apply path: the lists, the tables, the results and the header records
+    DevBuf ba_buf;
 };
 
 struct hpk_ctx {
@@ -72,6 +74,8 @@ struct hpk_ctx {
     int num_cu = 256;
     int decode_kernel = HPK_DECODE_AUTO;  // hpk_ctx_set_decode_kernel
     int block_scan = HPK_BLOCK_SCAN_HOST;  // hpk_ctx_set_block_scan
+    int block_apply = HPK_BLOCK_APPLY_HOST;  // hpk_ctx_set_block_apply
+    hpk_header* d_static = nullptr;  // hpk_static_table's 61 records, uploaded by the first hpk_apply_blocks
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
     uint32_t* d_lut2 = nullptr;
@@ -223,5 +227,14 @@ int hpk_launch_blkcount(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uin
 int hpk_launch_blkemit(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint32_t* block_off, uint32_t nblocks,
                        const uint32_t* field_off, const uint32_t* str_blk_off, hpk_field* fields, uint32_t fields_cap,
                        uint32_t* str_off, uint32_t* str_end, uint32_t strs_cap);
+
+// The header-block apply's kernel (hpk_blkapply.hip), on the ctx stream: hpk_apply_blocks' arguments as they are
+// (headers_cap clamped to 32 bits, as field_off's entries are) and the static records in device memory. results is
+// zeroed by the caller; fields, headers and tab_ent are 16-byte aligned.
+int hpk_launch_blkapply(hpk_ctx* c, const hpk_field* fields, const uint32_t* field_off, uint32_t nblocks, const uint32_t* out_off,
+                        const uint32_t* out_len, const uint8_t* status, uint32_t nstrs, uint32_t str_base, uint32_t static_base,
+                        const uint32_t* dec_blk_off, const uint32_t* dec_blk, uint32_t ndecs, hpk_dtab* tabs, hpk_header* tab_ent,
+                        uint64_t tab_ent_cap, hpk_header* headers, uint32_t headers_cap, hpk_block_result* results,
+                        const hpk_header* d_static);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

@@ -359,6 +359,29 @@ void scan_fields(const uint8_t* base, size_t begin, size_t end, std::vector<Fiel
 
 }  // namespace
 
+// RFC 7541 App. A as hpk_apply_blocks' kernel sees it (include/hpk.h): the names and values end to end, and the
+// entries as references into that text.
+extern "C" int hpk_static_table(const uint8_t** text, size_t* text_len, const hpk_header** entries) {
+    struct Image {
+        std::vector<uint8_t> text;
+        hpk_header ent[61];
+    };
+    static const Image img = [] {
+        Image m;
+        for (int k = 0; k < 61; ++k) {
+            const uint32_t nl = static_len(k, 0), vl = static_len(k, 1);
+            m.ent[k] = hpk_header{(uint32_t)m.text.size(), nl, (uint32_t)m.text.size() + nl, vl};
+            m.text.insert(m.text.end(), kStatic[k][0], kStatic[k][0] + nl);
+            m.text.insert(m.text.end(), kStatic[k][1], kStatic[k][1] + vl);
+        }
+        return m;
+    }();
+    if (text) *text = img.text.data();
+    if (text_len) *text_len = img.text.size();
+    if (entries) *entries = img.ent;
+    return HPK_E_OK;
+}
+
 // Decoder state: the dynamic table (lib.rs:43-164) and the SizeUpdate limit (decoder.rs:316-318).
 // The table holds its entries' bytes in one buffer, appended at the end, and the entries (offset,
 // name length, value length) in a ring, newest first: an insertion or eviction allocates nothing
@@ -779,14 +802,24 @@ void apply_block_dev(hpk_hdec* d, const hpk_field* fields, uint32_t nfields, con
 // every string; the host threads apply once everything is back, so a device failure leaves every decoder as it
 // was. Placement as the default path's: a decoder's blocks on one thread, in order, buckets placed by the work
 // (fields + 1 per block) that field_off states.
+int apply_blkdev_host(const hpk_blkdev& h, hpk_hdec* const* decs, const uint32_t* block_off, uint32_t nblocks, hpk_blocks_out* out,
+                      int nth, const Parallel& parallel, bool timing);
+
 int decode_blocks_device(hpk_ctx* ctx, hpk_hdec* const* decs, const uint8_t* blocks, const uint32_t* block_off,
                          uint32_t nblocks, hpk_blocks_out* out, int nth, const Parallel& parallel, bool timing) {
+    hpk_blkdev h;
+    if (int rc = hpk_blocks_device(ctx, blocks, block_off, nblocks, &h)) return rc;
+    return apply_blkdev_host(h, decs, block_off, nblocks, out, nth, parallel, timing);
+}
+
+// The device-scan path's host apply over what hpk_blocks_device brought back (also the device-apply path's, for a
+// call in which a block was deferred).
+int apply_blkdev_host(const hpk_blkdev& h, hpk_hdec* const* decs, const uint32_t* block_off, uint32_t nblocks, hpk_blocks_out* out,
+                      int nth, const Parallel& parallel, bool timing) {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto us = [&](std::chrono::steady_clock::time_point a) {
         return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
     };
-    hpk_blkdev h;
-    if (int rc = hpk_blocks_device(ctx, blocks, block_off, nblocks, &h)) return rc;
     auto t_2 = now();
     BlockScratch& W = t_scratch;
     if ((int)W.outs.size() < nth) W.outs.resize(nth);
@@ -832,6 +865,127 @@ int decode_blocks_device(hpk_ctx* ctx, hpk_hdec* const* decs, const uint8_t* blo
     return HPK_E_OK;
 }
 
+// hpk_hdec_decode_blocks with HPK_BLOCK_APPLY_DEVICE (include/hpk.h has the steps): the blocks grouped by decoder,
+// the tables out as hpk_dtab / hpk_header records over a blob of their bytes, the device pipeline with the apply
+// kernel at its end, and either the finished headers and tables back, or (a block deferred) the device-scan path's
+// host apply for the whole call. No decoder is written before everything is back.
+int decode_blocks_apply_device(hpk_ctx* ctx, hpk_hdec* const* decs, const uint8_t* blocks, const uint32_t* block_off,
+                               uint32_t nblocks, hpk_blocks_out* out, int nth, const Parallel& parallel, bool timing) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [&](std::chrono::steady_clock::time_point a) {
+        return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
+    };
+    if (nblocks == 0) return decode_blocks_device(ctx, decs, blocks, block_off, nblocks, out, nth, parallel, timing);
+    const auto t_0 = now();
+    uint32_t ring = 0, chunk = 0, wgd = 0;
+    (void)hpk_test_blkapply_geometry(&ring, &chunk, &wgd);
+    // the blocks by decoder: ids in order of first appearance, a counting pass, the lists
+    std::unordered_map<const hpk_hdec*, uint32_t> ids;
+    std::vector<hpk_hdec*> uniq;
+    std::vector<uint32_t> dec_of(nblocks), dec_blk_off(1, 0u), dec_blk(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        if (b && decs[b] == decs[b - 1]) {  // (a connection's blocks tend to come together)
+            dec_of[b] = dec_of[b - 1];
+            continue;
+        }
+        auto it = ids.emplace(decs[b], (uint32_t)uniq.size());
+        if (it.second) uniq.push_back(decs[b]);
+        dec_of[b] = it.first->second;
+    }
+    const uint32_t nd = (uint32_t)uniq.size();
+    dec_blk_off.assign(nd + 1, 0u);
+    for (uint32_t b = 0; b < nblocks; ++b) dec_blk_off[dec_of[b] + 1] += 1u;
+    for (uint32_t k = 0; k < nd; ++k) dec_blk_off[k + 1] += dec_blk_off[k];
+    {
+        std::vector<uint32_t> at(dec_blk_off.begin(), dec_blk_off.end() - 1);
+        for (uint32_t b = 0; b < nblocks; ++b) dec_blk[at[dec_of[b]]++] = b;
+    }
+    // the tables: the arena is the static text, then these prior bytes, then the packed strings
+    const uint8_t* stext = nullptr;
+    size_t stext_len = 0;
+    (void)hpk_static_table(&stext, &stext_len, nullptr);
+    std::vector<hpk_dtab> tabs(nd);
+    std::vector<hpk_header> ent;
+    std::vector<uint8_t> prior;
+    bool fits = true;  // every table within the device ring
+    for (uint32_t k = 0; k < nd && fits; ++k) {
+        const hpk_hdec* d = uniq[k];
+        fits = d->max_size <= 32ull * ring && d->count <= ring;
+        if (!fits) break;
+        // room for the table at the larger of its limit, the default and the SETTINGS limit, within the ring
+        size_t want = std::max<size_t>(d->max_size, 4096);
+        if (d->has_max_allowed) want = std::max(want, d->max_allowed);
+        const uint32_t cap = (uint32_t)std::min<size_t>(ring, std::max<size_t>((want + 31) / 32, d->count));
+        tabs[k] = hpk_dtab{(uint32_t)ent.size(), cap, d->count, (uint32_t)d->size, (uint32_t)d->max_size,
+                           d->has_max_allowed && d->max_allowed < HPK_DTAB_NO_LIMIT ? (uint32_t)d->max_allowed : HPK_DTAB_NO_LIMIT,
+                           0u, 0u};
+        const size_t e0 = ent.size();
+        ent.resize(e0 + cap, hpk_header{0u, 0u, 0u, 0u});
+        for (uint32_t i = 0; i < d->count; ++i) {
+            const hpk_hdec::Ent& e = d->at(i);
+            const uint32_t at = (uint32_t)(stext_len + prior.size());
+            ent[e0 + i] = hpk_header{at, e.nl, at + e.nl, e.vl};
+            prior.insert(prior.end(), d->bytes.data() + e.at, d->bytes.data() + e.at + e.nl + e.vl);
+        }
+    }
+    const uint64_t str_base = (uint64_t)stext_len + prior.size();
+    fits = fits && str_base + hpk_decoded_bound(block_off[nblocks]) + 16u < (1ull << 32) && ent.size() < (1ull << 32);
+    if (!fits) return decode_blocks_device(ctx, decs, blocks, block_off, nblocks, out, nth, parallel, timing);
+    hpk_applyplan plan{};
+    plan.dec_blk_off = dec_blk_off.data();
+    plan.dec_blk = dec_blk.data();
+    plan.ndecs = nd;
+    plan.tabs = tabs.data();
+    plan.tab_ent = ent.data();
+    plan.nent = (uint32_t)ent.size();
+    plan.str_base = (uint32_t)str_base;
+    const long us_export = us(t_0);
+    hpk_blkdev h;
+    if (int rc = hpk_blocks_device(ctx, blocks, block_off, nblocks, &h, &plan)) return rc;
+    if (!plan.applied) return apply_blkdev_host(h, decs, block_off, nblocks, out, nth, parallel, timing);
+    // everything is back: the outputs, then the decoders
+    const auto t_1 = now();
+    out->n_blocks = nblocks;
+    out->arena_len = (size_t)str_base + plan.packed_len;
+    out->n_headers = h.nfields;
+    out->arena = (uint8_t*)g_out_cache.take(0, out->arena_len);
+    out->headers = (hpk_header*)g_out_cache.take(1, (size_t)h.nfields * sizeof(hpk_header));
+    out->blocks = (hpk_block_result*)g_out_cache.take(2, (size_t)nblocks * sizeof(hpk_block_result));
+    if (!out->arena || !out->headers || !out->blocks) {
+        hpk_blocks_out_free(out);
+        return HPK_E_INVAL;
+    }
+    memcpy(out->arena, stext, stext_len);
+    if (!prior.empty()) memcpy(out->arena + stext_len, prior.data(), prior.size());
+    parallel([&](int t) {  // the packed bytes, the header records and the results, a slice per thread
+        auto slice = [&](void* to, const void* from, size_t bytes) {
+            const size_t lo = bytes * (size_t)t / (size_t)nth, hi = bytes * (size_t)(t + 1) / (size_t)nth;
+            if (hi > lo) memcpy((uint8_t*)to + lo, (const uint8_t*)from + lo, hi - lo);
+        };
+        slice(out->arena + str_base, h.arena, plan.packed_len);
+        slice(out->headers, plan.headers, (size_t)h.nfields * sizeof(hpk_header));
+        slice(out->blocks, plan.results, (size_t)nblocks * sizeof(hpk_block_result));
+    });
+    for (uint32_t k = 0; k < nd; ++k) {  // each table from its final entries' bytes, oldest first
+        hpk_hdec* d = uniq[k];
+        const hpk_dtab& t = plan.tabs_out[k];
+        d->count = 0;
+        d->size = 0;
+        d->end = 0;
+        d->max_size = t.max_size;
+        for (uint32_t i = t.count; i-- > 0;) {
+            const hpk_header& e = plan.ent_out[t.ent + i];
+            d->add(out->arena + e.name_off, e.name_len, out->arena + e.value_off, e.value_len);
+        }
+    }
+    if (timing)
+        fprintf(stderr,
+                "hpk_hdec_decode_blocks: device apply, %u decoders, tables out %ld us, device scan %ld us, strings %ld us, "
+                "apply and results back %ld us, outputs and tables in %ld us\n",
+                nd, us_export, h.us_scan, h.us_strings - plan.us_apply, plan.us_apply, us(t_1));
+    return HPK_E_OK;
+}
+
 }  // namespace
 
 // Timeline of a call with a device context: scan (threads) -> the batch assembled in the pinned
@@ -859,6 +1013,8 @@ extern "C" int hpk_hdec_decode_blocks(hpk_ctx* ctx, hpk_hdec* const* decs, const
     auto us = [&](std::chrono::steady_clock::time_point a) {
         return (long)std::chrono::duration_cast<std::chrono::microseconds>(now() - a).count();
     };
+    if (ctx && hpk_ctx_block_apply(ctx) == HPK_BLOCK_APPLY_DEVICE)  // opt-in: scan, strings and apply on the device
+        return decode_blocks_apply_device(ctx, decs, blocks, block_off, nblocks, out, nth, parallel, timing);
     if (ctx && hpk_ctx_block_scan(ctx) == HPK_BLOCK_SCAN_DEVICE)  // opt-in: scan and strings on the device
         return decode_blocks_device(ctx, decs, blocks, block_off, nblocks, out, nth, parallel, timing);
     // pass 1: scan every block, gather the Huffman strings (contiguous block ranges per thread)

@@ -25,5 +25,30 @@ struct hpk_blkdev {
     uint32_t nfields, nstrs;
     long us_scan, us_strings, us_back;  // wall times: upload, count, scans, totals / emit, string decode, arrays / bytes
 };
-int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o);
+// With a plan (HPK_BLOCK_APPLY_DEVICE), hpk_apply_blocks' kernel runs behind those steps. The arena it refers to is
+// the host's to build: the static text at 0, the tables' prior bytes behind it, the packed strings at str_base; no
+// byte of it goes to the device, which moves references only. applied says which set of outputs is back.
+struct hpk_applyplan {
+    // in (host memory): every block in exactly one decoder's list, the tables as hpk_apply_blocks takes them
+    const uint32_t* dec_blk_off;
+    const uint32_t* dec_blk;
+    uint32_t ndecs;
+    const hpk_dtab* tabs;
+    const hpk_header* tab_ent;
+    uint32_t nent;
+    uint32_t str_base;
+    // out (the page-locked area). applied == 1: no block was deferred; results (nblocks), tabs_out (ndecs), headers
+    // (hpk_blkdev.nfields records, those no block covers zero), ent_out (nent) and, in hpk_blkdev.arena, packed_len
+    // packed bytes; the rest of hpk_blkdev is not filled. applied == 0: hpk_blkdev as without a plan.
+    int applied;
+    const hpk_block_result* results;
+    const hpk_dtab* tabs_out;
+    const hpk_header* headers;
+    const hpk_header* ent_out;
+    uint32_t packed_len;
+    long us_apply;  // wall time: the uploads, the kernel, results and tables back
+};
+int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o,
+                      hpk_applyplan* plan = nullptr);
 int hpk_ctx_block_scan(const hpk_ctx* c);  // hpk_ctx_set_block_scan's value (HPK_BLOCK_SCAN_HOST for no context)
+int hpk_ctx_block_apply(const hpk_ctx* c);  // hpk_ctx_set_block_apply's value (HPK_BLOCK_APPLY_HOST for no context)
