@@ -49,8 +49,10 @@ constexpr int kWaves = 16, kW = 40960, kO = 79104, kQ = 2048, kRefillN = 2;
 using Geo = Geo12<kWaves, kW, kO, kQ>;
 // Wave-fill kernel (v25, hpk_wave.h): per wave a 3,008-byte window and a 5,040-byte image (v39: 8,048 bytes
 // per wave beside the 13-bit table; until v38 3,072 + 5,888, the image's last 256 the dummy slots), the
-// workgroup's range handed out in chunks of 224 literals; it runs every batch (HPK_WAVE_MIN is 0) unless the
-// context forces the workgroup-fill kernel (hpk_ctx_set_decode_kernel)
+// workgroup's range handed out in chunks of 224 literals; it runs every batch (since round 6; it had taken
+// those of >= 4M literals: config 2 40.3-40.8 vs 47.1-47.3 us for the workgroup-fill kernel, 1k-literal
+// synchronous calls 21.5 vs 24.4 us) unless the context forces the workgroup-fill kernel
+// (hpk_ctx_set_decode_kernel)
 #ifndef HPK_WAVE_WIN
 #define HPK_WAVE_WIN 3008  // (config 5: 2880 696.0-701.9, 3008 681.7-691.0, 3136 761.3-767.5 us: a fourth window round)
 #endif
@@ -58,21 +60,11 @@ using Geo = Geo12<kWaves, kW, kO, kQ>;
 #define HPK_WAVE_IMG (8048 - HPK_WAVE_WIN)
 #endif
 constexpr int kWaveWin = HPK_WAVE_WIN, kWaveImg = HPK_WAVE_IMG;
-#ifndef HPK_WAVE_MIN
-#define HPK_WAVE_MIN 0u  // least literals of a batch the wave kernel takes in HPK_DECODE_AUTO: every batch since round 6
-                         // (it had been 4M: config 2 40.3-40.8 vs 47.1-47.3 us for the workgroup-fill kernel,
-                         // 1k-literal synchronous calls 21.5 vs 24.4 us)
-#endif
-#ifndef HPK_WAVE_GUIDED
-#define HPK_WAVE_GUIDED 1  // chunks claimed by the waves (1: guided self-scheduling, 2: fixed HPK_WAVE_CHUNK) vs a static 1/16 each (0)
-#endif
-#ifndef HPK_WAVE_RANK
-#define HPK_WAVE_RANK 0  // longest-first order: 0 LDS counting sort (32 classes), 1/2 ballots (16/32 classes)
-#endif
 #ifndef HPK_WAVE_CHUNK
 #define HPK_WAVE_CHUNK 224u  // least literals per chunk claim
 #endif
-#define WAVE_KERNEL(m) hpk_decode_wave<m, kWaveWin, kWaveImg, HPK_WAVE_CHUNK, HPK_WAVE_GUIDED, HPK_WAVE_RANK>
+// (the waves claim their chunks by guided self-scheduling: kGuided 1, hpk_wave.h)
+#define WAVE_KERNEL(m) hpk_decode_wave<m, kWaveWin, kWaveImg, HPK_WAVE_CHUNK, 1>
 // (round 6) batches below HPK_WAVE_GUIDED_MIN literals hand their workgroups' ranges out in fixed chunks of
 // about one fill (config 2 with 104-literal chunks: 43.7-43.9 us against 51.1 guided, 44.1-45.0 static, 46.9
 // for the workgroup-fill kernel; with the overlapped start, hpk_wave.h, and 96-literal chunks 40.3-40.6)
@@ -83,14 +75,14 @@ constexpr int kWaveWin = HPK_WAVE_WIN, kWaveImg = HPK_WAVE_IMG;
 #define HPK_WAVE_SMALL_CHUNK 96u  // (config 2: 88 43.1-43.5, 92 40.5-41.0, 96 40.3-40.6, 100 42.4-43.3, 104 43.3-43.9 us;
                                   // v39, fills of ~108 literals: 92 36.5-37.0, 96 36.4-37.8, 100 38.1-38.4)
 #endif
-#define WAVE_KERNEL_SMALL(m) hpk_decode_wave<m, kWaveWin, kWaveImg, HPK_WAVE_SMALL_CHUNK, 2, HPK_WAVE_RANK>
+#define WAVE_KERNEL_SMALL(m) hpk_decode_wave<m, kWaveWin, kWaveImg, HPK_WAVE_SMALL_CHUNK, 2>
 #define DEC_KERNEL(m) hpk_decode12<m, kWaves, kW, kO, kQ, kRefillN>
 
 #ifdef HPK_DIAG
 // Diagnostic build (libhpk_diag.so, `make diag`; never the product library): HPK_DEBUG_MODE selects
 // 1 no decode, 2 no output stores, 3 per-wave stamps (16 x u64 per wave, hpk_debug_stamps),
 // 4 every store bounds-checked (fill kernel, hpk_debug_check), 5 per-wave counters of the long-literal
-// phase, 6 VALU sensitivity, 8-10 LDS conflict attribution (wave kernel, lit12_body's kDup: the table
+// phase, 8-10 LDS conflict attribution (wave kernel, lit12_body's kDup: the table
 // reads / the window read / the byte stores issued twice).
 static int g_debug_mode = -1;
 static unsigned long long* g_dbg = nullptr;
@@ -238,11 +230,14 @@ int hpk_persist_call(hpk_ctx* c, const hpk_batch& b, bool* handled) {
 }
 
 // The compacted form: the wave-fill kernel's (each workgroup packs into its range's bound span, no device
-// cursor: *wave = 1, out_off[n] is then the bound layout's end) for the batches the region form runs it
-// on, else the workgroup-fill kernel's (fills packed from the device cursor, *wave = 0)
-bool hpk_compact_wave(const hpk_ctx* c, uint32_t n) {
-    return c->decode_kernel == HPK_DECODE_WAVE || (c->decode_kernel == HPK_DECODE_AUTO && n >= HPK_WAVE_MIN);
+// cursor: *wave = 1, out_off[n] is then the bound layout's end) unless the context forces the workgroup-fill
+// kernel's (fills packed from the device cursor, *wave = 0); HPK_DECODE_AUTO selects the wave kernel for
+// every batch, as the region form does
+static bool wave_selected(const hpk_ctx* c) {
+    return c->decode_kernel == HPK_DECODE_WAVE || c->decode_kernel == HPK_DECODE_AUTO;
 }
+
+bool hpk_compact_wave(const hpk_ctx* c, uint32_t) { return wave_selected(c); }
 
 int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, uint32_t* long_list, uint32_t* cursor,
                               bool wave) {
@@ -256,7 +251,7 @@ int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, 
     a.long_big = HPK_LONG_BIG;
     if (wave) {
         a.cursor = nullptr;  // (the huge phase takes a listed literal's region from co_off)
-        hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, HPK_WAVE_CHUNK, HPK_WAVE_GUIDED, HPK_WAVE_RANK, true>),
+        hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, HPK_WAVE_CHUNK, 1, true>),
                            dim3(decode_blocks(c, b)), dim3(Geo::kBlock), 0, c->stream, a);
     } else {
         hipLaunchKernelGGL((hpk_decode12<0, kWaves, kW, kO, kQ, kRefillN, true>), dim3(decode_blocks(c, b)),
@@ -268,7 +263,7 @@ int hpk_launch_decode_compact(hpk_ctx* c, const hpk_batch& b, uint32_t* co_off, 
 
 extern "C" int hpk_test_decode_geometry(int kind, uint32_t* out13) {
     if (!out13 || (kind != HPK_DECODE_FILL && kind != HPK_DECODE_WAVE)) return HPK_E_INVAL;
-    using GW = GeoW<kWaveWin, kWaveImg, HPK_WAVE_TAB>;
+    using GW = GeoW<kWaveWin, kWaveImg, kWaveTab>;
     out13[0] = kind == HPK_DECODE_WAVE ? GW::kBlock : Geo::kBlock;
     out13[1] = HPK_HUGE_MIN;
     out13[2] = kHugeMax;
@@ -281,7 +276,7 @@ extern "C" int hpk_test_decode_geometry(int kind, uint32_t* out13) {
     out13[9] = HPK_LONG_CLAIM;
     out13[10] = HPK_LONG_WAVES;
     out13[11] = HPK_LONG_OS;
-    out13[12] = kind == HPK_DECODE_WAVE ? HPK_WAVE_TAB : 2;  // huge_phase / long_phase's kTab
+    out13[12] = kind == HPK_DECODE_WAVE ? kWaveTab : 2;  // huge_phase / long_phase's kTab
     return HPK_E_OK;
 }
 
@@ -297,30 +292,12 @@ int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b, uint32_t* long_list) {
 #endif
     const uint32_t blocks = decode_blocks(c, b);
     const dim3 grid(blocks), block(Geo::kBlock);
-    bool wave = c->decode_kernel == HPK_DECODE_WAVE || (c->decode_kernel == HPK_DECODE_AUTO && b.n >= HPK_WAVE_MIN);
+    bool wave = wave_selected(c);
 #ifdef HPK_DIAG
     if (const char* wk = getenv("HPK_DECODE_KERNEL")) wave = wk[0] == 'w';  // "wave" / "fill" (A/B runs)
     if (g_debug_mode < 0) {
         const char* dm = getenv("HPK_DEBUG_MODE");
         g_debug_mode = dm ? atoi(dm) : 0;
-    }
-    // (A/B runs) HPK_WAVE_VARIANT=v: hand-out v / 3 (0 static, 1 guided), order v % 3 (kRank)
-    static const int wave_var = getenv("HPK_WAVE_VARIANT") ? atoi(getenv("HPK_WAVE_VARIANT")) : -1;
-    if (wave && wave_var >= 0 && g_debug_mode == 0) {
-        switch (wave_var) {
-            case 0: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, false, 0>), grid, block, 0, c->stream, a); break;
-            case 1: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, false, 1>), grid, block, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, false, 2>), grid, block, 0, c->stream, a); break;
-            case 3: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, true, 0>), grid, block, 0, c->stream, a); break;
-            case 4: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, true, 1>), grid, block, 0, c->stream, a); break;
-            case 5: hipLaunchKernelGGL((hpk_decode_wave<0, kWaveWin, kWaveImg, 224u, true, 2>), grid, block, 0, c->stream, a); break;
-            // (the least chunk of the guided hand-out, 128-1024 literals: within the noise, r3l; the 3072 /
-            // 5888 split won over 3328-3840 B windows, whose fourth prefetch round spills, r3i; dword
-            // output by LDS masked OR, code in git history: 1223-1229 us, r3o)
-            default: hipLaunchKernelGGL((WAVE_KERNEL(0)), grid, block, 0, c->stream, a); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return HPK_E_OK;
     }
     // modes 3 and 5 write per-wave entries (16 each) into a.dbg; mode 5 adds to them, so they start zeroed
     if (g_debug_mode == 3 || g_debug_mode == 5) {
@@ -339,7 +316,7 @@ int hpk_launch_decode(hpk_ctx* c, const hpk_batch& b, uint32_t* long_list) {
     case m: hipLaunchKernelGGL(DEC_KERNEL(m), grid, block, 0, c->stream, a); break;
     if (wave) {
         switch (g_debug_mode) {
-            WAVE_MODE(1) WAVE_MODE(2) WAVE_MODE(3) WAVE_MODE(5) WAVE_MODE(6) WAVE_MODE(8) WAVE_MODE(9) WAVE_MODE(10)
+            WAVE_MODE(1) WAVE_MODE(2) WAVE_MODE(3) WAVE_MODE(5) WAVE_MODE(8) WAVE_MODE(9) WAVE_MODE(10)
             default: WAVE_MODE(0)
         }
     } else {

@@ -229,9 +229,6 @@ __global__ __launch_bounds__(kWaves * 64) void hpk_decode12(DecodeArgs a) {
     // each thread stores its literals' bytes (round 5: unaligned 16-byte pieces, as the wave kernel's
     // compact_fill; the round-4 per-chunk gather measured 97 us on config 2 against 90-91), lengths,
     // statuses and offsets. Listed literals (kListed) are 0 bytes here.
-#ifndef HPK_COMPACT_NOCOPY
-#define HPK_COMPACT_NOCOPY 0  // (measurement only: no copy, no lengths)
-#endif
     auto compact_flush = [&](uint32_t fcur, uint32_t fk, uint32_t kqc) {
         lds_barrier();  // every length and status of the fill is in s_lenst; the window is free
         uint32_t* const s_iof = reinterpret_cast<uint32_t*>(s_in);  // [kQ] image offsets by literal
@@ -277,7 +274,7 @@ __global__ __launch_bounds__(kWaves * 64) void hpk_decode12(DecodeArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const uint32_t t = tid + (uint32_t)G::kBlock * r;
-            if (t < fk && lst[r] != kListed && !HPK_COMPACT_NOCOPY) {
+            if (t < fk && lst[r] != kListed) {
                 a.co_off[fcur + t] = base + exs[r];
                 a.out_len[fcur + t] = lenof(lst[r]);
                 a.status[fcur + t] = (uint8_t)(lst[r] >> 24);
@@ -290,7 +287,7 @@ __global__ __launch_bounds__(kWaves * 64) void hpk_decode12(DecodeArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const uint32_t t = tid + (uint32_t)G::kBlock * r;
-            const uint32_t np = t < fk && !HPK_COMPACT_NOCOPY ? lenof(lst[r]) : 0u;
+            const uint32_t np = t < fk ? lenof(lst[r]) : 0u;
             const uint32_t sp = np ? s_iof[t] : 0u, dp = D0 + exs[r];
             auto dw_at = [&](uint32_t u) {
                 return __builtin_amdgcn_alignbyte(img32[(u >> 2) + 1u], img32[u >> 2], u & 3u);

@@ -93,12 +93,9 @@ __device__ __forceinline__ void pin(uint32_t x) { asm volatile("" ::"v"(x)); }
 #define HPK_LONG_RING 32  // input ring dwords per lane
 #endif
 
-#ifndef HPK_LONG_TAILPT
-#define HPK_LONG_TAILPT 1  // round 6: the steps between refill points are body steps only (>= kBodyMin bits left);
-                           // a literal's last bits are walked with checked steps at the refill point, by the
-                           // lanes in their tail only (both step kinds in one loop made every step pay both:
-                           // some lane of 64 is nearly always in its tail)
-#endif
+// Round 6: the steps between refill points are body steps only (>= kBodyMin bits left); a literal's last bits are
+// walked with checked steps at the refill point, by the lanes in their tail only (both step kinds in one loop made
+// every step pay both: some lane of 64 is nearly always in its tail).
 
 #ifndef HPK_LONG_CH
 #define HPK_LONG_CH 3  // 16-byte chunks a lane loads per refill point (round 6: 3, config 3 633.0-634.1 vs 641.7-642.4 us)
@@ -113,10 +110,6 @@ __device__ __forceinline__ void pin(uint32_t x) { asm volatile("" ::"v"(x)); }
 // s_q), kU steps between refill points, kRing input dwords per lane in s_ring and a kOS-byte
 // output buffer per lane in s_out (16-byte aligned). kDiag (diagnostic builds): per-wave counters
 // into a.dbg[wave * 16 + i] (scripts/diag_decode.py).
-#ifndef HPK_LONG_BODY
-#define HPK_LONG_BODY 1  // v28: body steps (no fit tests) while a literal has >= kBodyMin bits left
-#endif
-
 __device__ __forceinline__ uint32_t lpt_class_of(uint32_t nb) { return 31u - min(nb >> 7, 31u); }
 
 template <int kBlock, int kU, int kRing, int kDiag, int kBlockAll, int kOSz = HPK_LONG_OS, int kClaim = 64,
@@ -136,10 +129,10 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
     // front, so a period starts with <= 15 bytes and adds <= 5 per step: 15 + 5 kU + 3 bytes
     // (a step's 4-byte store) must fit.
     constexpr uint32_t kOS = kOSz;
-    // (HPK_LONG_TAILPT: a tail at the refill point adds <= 6 bytes: < body_min <= 31 bits, codes of >= 5 bits;
+    // (a tail at the refill point adds <= 6 bytes: < body_min <= 31 bits, codes of >= 5 bits;
     // a body step adds <= 5 whatever the table's width: four codes of its two entries and a long one)
     static_assert(body_min<kTab>() <= 35u, "a tail's bytes");
-    static_assert(15 + 5 * kU + 3 + (HPK_LONG_TAILPT ? 6 : 0) < (int)kOS, "output buffer");
+    static_assert(15 + 5 * kU + 3 + 6 < (int)kOS, "output buffer");
     static_assert((kRing & (kRing - 1)) == 0 && kRing >= 16 && 4 * kCh + 8 <= kRing, "input ring: a power of two >= 16 dwords");
     static_assert(kBlock % 64 == 0 && kBlock <= kBlockAll, "decoding waves");
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -200,69 +193,67 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
             d2 = ring[(j + 1u) * kBlock];
             live = true;
         }
-        // 2b. (HPK_LONG_TAILPT) lanes whose literal has fewer than kBodyMin bits left, all of its chunks in
+        // 2b. lanes whose literal has fewer than kBodyMin bits left, all of its chunks in
         // the ring: checked steps (lit12_step's) until the walk ends; the literal is finished in 4 below
-        if (HPK_LONG_TAILPT) {
-            for (;;) {
-                const bool tl = act && live && !done && Eb - X < body_min<kTab>() && h * 4u >= span;
-                if (!__any(tl)) break;
-                if (tl) {
-                    const uint32_t j0 = X >> 5;
-                    const uint32_t d3 = ring[((j0 + 2u) & (kRing - 1u)) * kBlock];
-                    const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, ~X);
-                    const uint32_t rem = Eb - X;
-                    const uint32_t e1 = s_lut[w >> (32 - lut_bits<kTab>())];
-                    bool a1, a2;
-                    const uint32_t u1 = lut12<kTab>(e1, rem, a1, a2);
-                    bool park = !a1 & (rem > lut_bits<kTab>());
-                    const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
-                    const uint32_t rem2 = rem - u1;
-                    const uint32_t e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
-                    bool b1, b2;
-                    const uint32_t v2 = lut12<kTab>(e2, rem2, b1, b2);
-                    park |= cont & !b1 & (rem2 > lut_bits<kTab>());
-                    b1 &= cont;
-                    b2 &= cont;
-                    const uint32_t g1 = (uint32_t)a1 + (uint32_t)a2, g2 = (uint32_t)b1 + (uint32_t)b2;
-                    uint8_t* const p = obuf + (ob - lb);
-                    p[0] = (uint8_t)e1;
-                    p[1] = (uint8_t)(e1 >> 16);
-                    p[g1] = (uint8_t)e2;
-                    p[g1 + 1] = (uint8_t)(e2 >> 16);
-                    ob += g1 + g2;
-                    const uint32_t xn = X + u1 + (cont ? v2 : 0u);
-                    const bool cross = (xn ^ X) > 31u;
-                    d0 = cross ? d1 : d0;
-                    d1 = cross ? d2 : d1;
-                    d2 = cross ? d3 : d2;
-                    X = xn;
-                    bool prog = a1 | park;
-                    // both entries used whole: more codes may follow; otherwise the walk has ended
-                    const bool mo = park | (b1 & (b2 | lut_nottwo<kTab>(e2)));
-                    if (park) {  // a 13..30-bit code or EOS with > 12 bits left
-                        const uint32_t wp = __builtin_amdgcn_alignbit(d0, d1, ~X);
-                        uint32_t sy, len;
-                        bool eos;
-                        lo_decode(wp, s_lo, sy, len, eos);
-                        if (len > Eb - X) {  // huffman.rs:128-134
-                            st = HPK_PADDING_TOO_LARGE;
-                            prog = false;
-                        } else if (eos) {  // huffman.rs:112-116
-                            st = HPK_EOS_IN_STRING;
-                            prog = false;
-                        } else {
-                            obuf[ob - lb] = (uint8_t)sy;
-                            ob += 1u;
-                            const uint32_t xp = X + len;
-                            const uint32_t j = xp >> 5;
-                            d0 = ring[((j - 1u) & (kRing - 1u)) * kBlock];
-                            d1 = ring[(j & (kRing - 1u)) * kBlock];
-                            d2 = ring[((j + 1u) & (kRing - 1u)) * kBlock];
-                            X = xp;
-                        }
+        for (;;) {
+            const bool tl = act && live && !done && Eb - X < body_min<kTab>() && h * 4u >= span;
+            if (!__any(tl)) break;
+            if (tl) {
+                const uint32_t j0 = X >> 5;
+                const uint32_t d3 = ring[((j0 + 2u) & (kRing - 1u)) * kBlock];
+                const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, ~X);
+                const uint32_t rem = Eb - X;
+                const uint32_t e1 = s_lut[w >> (32 - lut_bits<kTab>())];
+                bool a1, a2;
+                const uint32_t u1 = lut12<kTab>(e1, rem, a1, a2);
+                bool park = !a1 & (rem > lut_bits<kTab>());
+                const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
+                const uint32_t rem2 = rem - u1;
+                const uint32_t e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
+                bool b1, b2;
+                const uint32_t v2 = lut12<kTab>(e2, rem2, b1, b2);
+                park |= cont & !b1 & (rem2 > lut_bits<kTab>());
+                b1 &= cont;
+                b2 &= cont;
+                const uint32_t g1 = (uint32_t)a1 + (uint32_t)a2, g2 = (uint32_t)b1 + (uint32_t)b2;
+                uint8_t* const p = obuf + (ob - lb);
+                p[0] = (uint8_t)e1;
+                p[1] = (uint8_t)(e1 >> 16);
+                p[g1] = (uint8_t)e2;
+                p[g1 + 1] = (uint8_t)(e2 >> 16);
+                ob += g1 + g2;
+                const uint32_t xn = X + u1 + (cont ? v2 : 0u);
+                const bool cross = (xn ^ X) > 31u;
+                d0 = cross ? d1 : d0;
+                d1 = cross ? d2 : d1;
+                d2 = cross ? d3 : d2;
+                X = xn;
+                bool prog = a1 | park;
+                // both entries used whole: more codes may follow; otherwise the walk has ended
+                const bool mo = park | (b1 & (b2 | lut_nottwo<kTab>(e2)));
+                if (park) {  // a 13..30-bit code or EOS with > 12 bits left
+                    const uint32_t wp = __builtin_amdgcn_alignbit(d0, d1, ~X);
+                    uint32_t sy, len;
+                    bool eos;
+                    lo_decode(wp, s_lo, sy, len, eos);
+                    if (len > Eb - X) {  // huffman.rs:128-134
+                        st = HPK_PADDING_TOO_LARGE;
+                        prog = false;
+                    } else if (eos) {  // huffman.rs:112-116
+                        st = HPK_EOS_IN_STRING;
+                        prog = false;
+                    } else {
+                        obuf[ob - lb] = (uint8_t)sy;
+                        ob += 1u;
+                        const uint32_t xp = X + len;
+                        const uint32_t j = xp >> 5;
+                        d0 = ring[((j - 1u) & (kRing - 1u)) * kBlock];
+                        d1 = ring[(j & (kRing - 1u)) * kBlock];
+                        d2 = ring[((j + 1u) & (kRing - 1u)) * kBlock];
+                        X = xp;
                     }
-                    done = !prog || !mo;
                 }
+                done = !prog || !mo;
             }
         }
         // 3. output to global memory: a literal's first 16-byte group (it shares it with the previous
@@ -423,7 +414,7 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
                                 : h * 4u >= span ? (uint32_t)kU
                                 : x5 + 4u <= h ? min((uint32_t)kU, ((h - x5 - 4u) >> 1) + 1u) : 0u;
         for (int s = 0; s < kU; ++s) {
-            const bool go = (uint32_t)s < budget && !done && (!HPK_LONG_TAILPT || Eb - X >= body_min<kTab>());
+            const bool go = (uint32_t)s < budget && !done && Eb - X >= body_min<kTab>();
             if (kDiag) {
                 dg[2] += (unsigned long long)__popcll(__ballot(go));
                 dg[3] += (unsigned long long)__popcll(__ballot(act && live && !done && !go));
@@ -435,38 +426,15 @@ __device__ __forceinline__ void long_phase(const DecodeArgs& a, uint32_t ba, uin
             const uint32_t j0 = X >> 5;
             const uint32_t d3 = ring[((j0 + 2u) & (kRing - 1u)) * kBlock];
             const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, ~X);
-            const uint32_t rem = Eb - X;
-            uint32_t e1, e2, u1, u2, g1, g2;
-            bool park, prog;
-            if (HPK_LONG_TAILPT || (HPK_LONG_BODY && rem >= body_min<kTab>())) {
-                // body step (lit12_body): every code of the two entries ends inside the literal
-                e1 = s_lut[w >> (32 - lut_bits<kTab>())];
-                u1 = lut_l3<kTab>() ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
-                e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
-                u2 = lut_l3<kTab>() ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
-                g1 = lut_l3<kTab>() ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1);
-                g2 = lut_l3<kTab>() ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2);
-                park = u2 == 0u;  // (more bits than the table's index left at e2: body_min less the index bits)
-                prog = true;
-            } else {
-                e1 = s_lut[w >> (32 - lut_bits<kTab>())];
-                bool a1, a2;
-                u1 = lut12<kTab>(e1, rem, a1, a2);
-                park = !a1 & (rem > lut_bits<kTab>());  // (see lit12_step)
-                const bool cont = a1 & (a2 | lut_nottwo<kTab>(e1));
-                const uint32_t w2 = w << u1;
-                const uint32_t rem2 = rem - u1;
-                e2 = s_lut[w2 >> (32 - lut_bits<kTab>())];
-                bool b1, b2;
-                const uint32_t v2 = lut12<kTab>(e2, rem2, b1, b2);
-                park |= cont & !b1 & (rem2 > lut_bits<kTab>());
-                b1 &= cont;
-                b2 &= cont;
-                g1 = (uint32_t)a1 + (uint32_t)a2;
-                g2 = (uint32_t)b1 + (uint32_t)b2;
-                u2 = cont ? v2 : 0u;
-                prog = a1 | park;
-            }
+            // a body step (lit12_body): every code of the two entries ends inside the literal
+            const uint32_t e1 = s_lut[w >> (32 - lut_bits<kTab>())];
+            const uint32_t u1 = lut_l3<kTab>() ? HPK_L3_HELD(e1) : HPK_L2_HELD(e1);
+            const uint32_t e2 = s_lut[(w << u1) >> (32 - lut_bits<kTab>())];
+            const uint32_t u2 = lut_l3<kTab>() ? HPK_L3_HELD(e2) : HPK_L2_HELD(e2);
+            const uint32_t g1 = lut_l3<kTab>() ? HPK_L3_CODES(e1) : HPK_L2_CODES(e1);
+            const uint32_t g2 = lut_l3<kTab>() ? HPK_L3_CODES(e2) : HPK_L2_CODES(e2);
+            const bool park = u2 == 0u;  // (more bits than the table's index left at e2: body_min less the index bits)
+            bool prog = true;
             {  // the step's (up to 4) bytes as byte stores into the lane's own buffer (bytes past the
                // ones decoded are overwritten later or never stored out; one unaligned dword store
                // instead: config 3 936.7 vs 889.7 us, gfx950 splits it)

@@ -264,14 +264,11 @@ __device__ __forceinline__ void lit12_step(Lit12& L, const uint32_t* __restrict_
 // literal's own region (see kBodyMin). Lengths come from the entries' "bits held" and "codes held" fields: ~25 VALU per
 // step against lit12_step's ~48. A lookup that holds no code (a 13..30-bit code or EOS) takes the
 // checked leading-ones branch of lit12_step; `body` says whether the next step may be a body step.
-#ifndef HPK_BODY_MIN
-#define HPK_BODY_MIN 29
-#endif
-// 24 bits a step may consume + 5: after a body step >= 5 bits are left, so when the decoded bytes end
+// kBodyMin is the 24 bits a step may consume + 5: after a body step >= 5 bits are left, so when the decoded bytes end
 // there the decoded length is below the bound (a code is >= 5 bits) and a garbage byte at the next
 // output position stays in the region; a lookup holding no code has >= 29 - 12 > 12 bits left, so it
 // always takes the leading-ones branch (whose symbol overwrites the garbage)
-constexpr uint32_t kBodyMin = HPK_BODY_MIN;
+constexpr uint32_t kBodyMin = 29;
 // The same for a table of b index bits is 2 b + 5 (12 bits: the 29 above; 13 bits: 31). A step then consumes
 // <= 2 b <= 26 bits, so it still crosses at most one dword and leaves >= 5 bits, and a lookup holding no code
 // has >= b + 5 > b bits left (13 bits: >= 18 > 13).

@@ -41,75 +41,24 @@
 #include "hpk_huge.h"
 #include "hpk_long.h"
 
-#ifndef HPK_BODY_UNROLL
-#define HPK_BODY_UNROLL 4  // body steps between the checks for a lane whose literal's body ended (2: config 5 +2.5 %;
-                           // v39, ~19.5 executed steps per fill: 3 678.5-699.9 against 681.7-691.0 us, within the spread)
-#endif
-#ifndef HPK_BODY_ROUND
-#define HPK_BODY_ROUND 3  // the lane loop's round of HPK_BODY_UNROLL body steps (v41): 0 = a step at a time, each under its
-                          // own `if (body)` (v40); 1 = nested steps (lit12_round, hpk_walk.h), long codes inline; 2 / 3 =
-                          // nested, long codes once a round (a parked lane drops out / stays in the round)
-#endif
-#ifndef HPK_WAVE_TAB
-#define HPK_WAVE_TAB 4  // the wave kernel's two-symbol table (lut_bits, hpk_walk.h): 4 = the LUT3 layout (byte-wide
-                        // "bits held", v28) at 13 index bits (v39); 3 = the same at 12 bits, 2 = LUT2
-#endif
-#ifndef HPK_CW_LANE_DIAG
-#define HPK_CW_LANE_DIAG 0  // (measurement only) 2: no copy loop, 3: 16-byte pieces at 16-aligned
-                            // addresses, 4: no 16-byte stores
-#endif
-#ifndef HPK_NT_STORE
-#define HPK_NT_STORE 1  // 1: the image write-back as nontemporal 16-byte stores (the output is never re-read)
-#endif
-#ifndef HPK_NT_LOAD
-#define HPK_NT_LOAD 1  // 1: the window prefetch as nontemporal 16-byte loads (each input byte is read once)
-#endif
-#ifndef HPK_TAIL_MASKED
-#define HPK_TAIL_MASKED 1  // 1: a literal's last <= 28 bits by the straight-line masked tail (lit12_tail, v38), the
-                           // checked tail loop only for lanes it leaves as slow; 0: the checked tail loop (v27)
-#endif
-#ifndef HPK_FLUSH_SPLIT
-#define HPK_FLUSH_SPLIT 1  // 1 (v40): the write-back in two parts, the image's LDS reads all issued before the sort
-                           // and its global stores after it, so the sort's LDS round trips run under the read-out;
-                           // 0: one round at a time, each store behind its own LDS wait (v39; config 5 677.6-682.1
-                           // us, split 675.9-679.5, split with HPK_PF_EARLY 672.7-676.2: profiles/frontend)
-#endif
-#ifndef HPK_PF_EARLY
-#define HPK_PF_EARLY 1  // 1 (v40): the next fill's loads issued ahead of the write-back's stores; 0: behind them (v39)
-#endif
-// Fill trim (v42): work around the lane loop that the result does not need, each part on its own switch.
-#ifndef HPK_TAIL_SAVED
-#define HPK_TAIL_SAVED 1  // 1: the first literal's masked tail starts from the state word saved when its body ended
-                          // (tail12_word: one register beside aX, aO, aSt), and only the tail's slow lanes reload
-                          // their window dwords; 0: every lane reloads three dwords before the tails (v38)
-#endif
-#ifndef HPK_ST_CARRY
-#define HPK_ST_CARRY 1  // 1: the first slot's status is the one its tail computed (tail12_end), the tail's slow lanes
-                        // taking theirs from their dword pair behind one wave-uniform test; 0: every lane re-reads the
-                        // window at its stop (win_at, two LDS reads) and computes the residual status again
-#endif
-#ifndef HPK_WIN_CUT
-#define HPK_WIN_CUT 1 // 1: the window loads stop at the literal chunk's last input byte (round 6: config-5
-                       // reads 1.229 -> 1.178 GB per launch, time unchanged)
-#endif
-
 namespace hpkdec {
 
+// The lane loop's round is kBodyUnroll body steps between the checks for a lane whose literal's body ended (2: config 5
+// +2.5 %; 3 and 6: within the spread or slower). kWaveTab is the wave kernel's two-symbol table (lut_bits,
+// hpk_walk.h): 4 = the LUT3 layout (byte-wide "bits held") at 13 index bits; the fills and the phases after them use it.
+constexpr int kBodyUnroll = 4;
+constexpr int kWaveTab = 4;
+
+// The image write-back and the window prefetch are nontemporal 16-byte accesses: the output is never re-read, and
+// each input byte is read once.
 typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st16(uint4* p, const uint4 v) {
-    if (HPK_NT_STORE) {
-        const v4u32 x = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(x, reinterpret_cast<v4u32*>(p));
-    } else {
-        *p = v;
-    }
+    const v4u32 x = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(x, reinterpret_cast<v4u32*>(p));
 }
 __device__ __forceinline__ uint4 ld16(const uint4* p) {
-    if (HPK_NT_LOAD) {
-        const v4u32 x = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(p));
-        return make_uint4(x.x, x.y, x.z, x.w);
-    }
-    return *p;
+    const v4u32 x = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(p));
+    return make_uint4(x.x, x.y, x.z, x.w);
 }
 
 // LDS map (v39): LO (1,920 B), the two-symbol table (4 B << lut_bits<kTab>: 32 KiB at 13 bits), the dummy
@@ -143,8 +92,7 @@ struct GeoW {
 // dense listing found an entry it cannot list, [7] chunks of kChunk literals handed out to the waves,
 // [8] huge literals listed (s_huge = s_ctr + 16, at most kHugeMax of them; hpk_huge.h), [9] (kCompact) bytes
 // of the workgroup's bound span handed out
-// kRank: 0 = counting sort with LDS atomics on 32 length classes of 2 bytes, 1 / 2 = ranks from
-// ballots over 16 classes of 4 bytes / 32 classes of 2 bytes (no LDS round trip)
+
 // Inclusive sum over the wave's 64 lanes: DPP row shifts within rows of 16 lanes (zero fill), then the
 // rows' totals by readlane.
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
@@ -164,9 +112,11 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
 // gathered into it (compact_fill), every listed literal takes its 4-rounded bound there when it is
 // listed (co_off). No device-wide cursor: one atomic per fill on one word would be ~290k per 32M-literal
 // launch, against the ~88 per us one word takes (MI355X_MICROARCH.md, dequeue).
-template <int kMode, int kWinB, int kImgB, uint32_t kChunk, int kGuided, int kRank, bool kCompact = false>
+// kGuided: how the workgroup's range is handed out to its waves (claim, below): 1 = guided self-scheduling, 2 =
+// fixed chunks of kChunk literals (0, a static 1/16 each: not instantiated, see claim).
+template <int kMode, int kWinB, int kImgB, uint32_t kChunk, int kGuided, bool kCompact = false>
 __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
-    constexpr int kTab = HPK_WAVE_TAB;  // the table of the fills and the phases after them
+    constexpr int kTab = kWaveTab;  // the table of the fills and the phases after them
     // (the stamps of diagnostic mode 3 need 832 bytes of LDS, and the product's geometry leaves none: there
     // every wave's image is 64 bytes smaller, 1.3 % fewer literals per fill)
     using G = GeoW<kWinB, kMode == 3 ? kImgB - 64 : kImgB, kTab>;
@@ -204,16 +154,17 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
     const uint32_t BA = (uint32_t)((uint64_t)a.n * blockIdx.x / gridDim.x);
     const uint32_t BB = (uint32_t)((uint64_t)a.n * (blockIdx.x + 1) / gridDim.x);
     // (round 6) The start's memory round trips overlapped: every wave's first chunk is fixed here (wave wv's
-    // c0 literals from BA + wv c0; the static split: its 1/16), and its first literal's offsets, the dense
-    // check's offsets and the tables are loaded together (they had been four dependent round trips: tables,
-    // the dense check, the first claim's offsets, then the first fill's). Config 2: see DESIGN.md §4.0.
+    // c0 literals from BA + wv c0; the static split: its 1/16), and its first literal's offsets, its chunk's
+    // end offset, the dense check's offsets and the tables are loaded together (they had been four dependent
+    // round trips: tables, the dense check, the first claim's offsets, then the first fill's). Config 2: see
+    // DESIGN.md §4.0.
     static_assert(G::kBlock == 1024, "the dense check's two offsets rounds");
     const uint32_t c0 = kGuided == 2 ? kChunk : max(kChunk, (BB - BA) / 32u);
     const uint32_t cur0 = kGuided == 0 ? BA + (uint32_t)((uint64_t)(BB - BA) * wv / G::kWaves) : min(BA + wv * c0, BB);
     const uint32_t ce0 =
         kGuided == 0 ? BA + (uint32_t)((uint64_t)(BB - BA) * (wv + 1) / G::kWaves) : min(cur0 + c0, BB);
     const uint32_t gin0 = a.in_off[cur0];
-    const uint32_t gend0 = HPK_WIN_CUT ? a.in_off[ce0] : 0u;
+    const uint32_t gend0 = a.in_off[ce0];
     const uint32_t gout0 = kCompact ? 0u : a.out_off[cur0];
     const uint32_t kd = min(BB - BA, 2048u);  // the dense check's literals: the range's first 2048
     uint32_t dv0[2], dv1[2];
@@ -368,7 +319,10 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
         // the others finished (11 % of a wave's time). Chunks shrink as the range drains (guided
         // self-scheduling: 1/32 of what is left, at least kChunk literals), so early chunks hold many
         // fills (a chunk's last fill is usually partial) and the last ones even the waves out.
-        // (!kGuided: the wave's static 1/16 of the range, then nothing)
+        // (kGuided 2, batches below HPK_WAVE_GUIDED_MIN literals: every chunk is kChunk literals, about one fill.
+        // !kGuided, the wave's static 1/16 of the range, then nothing: nothing instantiates it any more, and it
+        // stays in the source only because taking it out changes the guided region kernel's register
+        // allocation)
         bool given = false;
         auto claim = [&](uint32_t& ca, uint32_t& ce) {
             if (!kGuided) {
@@ -381,8 +335,8 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
             if (lane == 0) {
                 const uint32_t seen = *(volatile HPK_LDS_AS uint32_t*)(&s_ctr[7]);
                 const uint32_t left = BB - BA > seen ? BB - BA - seen : 0u;
-                // (2: fixed chunks. Round 6: fixed chunks until 16 were left, then 1/16 of what was left, at
-                // least 32 / 48 / 64 literals: config 2 47.1-47.8 / 45.2-45.5 / 44.1-44.6 vs 40.5-41.4 us)
+                // (Round 6: fixed chunks until 16 were left, then 1/16 of what was left, at least 32 / 48 / 64
+                // literals: config 2 47.1-47.8 / 45.2-45.5 / 44.1-44.6 vs 40.5-41.4 us)
                 const uint32_t want = kGuided == 2 ? kChunk : max(kChunk, left / 32u);
                 c = atomicAdd(&s_ctr[7], want);
                 c = c < BB - BA ? c : BB - BA;
@@ -398,16 +352,16 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
         uint32_t io0[2], oo0[2], ie = 0, oe = 0, pcnt = 1, pc = 0;
         uint4 ch[R];
         // clim: the last 16-byte input chunk of the current literal chunk's bytes, where the window loads
-        // stop (bytes past it belong to another wave's chunk: loaded here, they were loaded twice). (A ring,
-        // a window's first chunks moved in LDS from the previous window's unused tail instead of
-        // reloaded, read the same bytes from HBM, +2 % time: those reloads hit the L2)
-        constexpr bool kCut = HPK_WIN_CUT != 0;
+        // stop (bytes past it belong to another wave's chunk: loaded here, they were loaded twice; round 6:
+        // config 5 reads 1.229 -> 1.178 GB per launch, time unchanged). (A ring, a window's first chunks moved
+        // in LDS from the previous window's unused tail instead of reloaded, read the same bytes from HBM,
+        // +2 % time: those reloads hit the L2)
         constexpr uint32_t kWinC = (uint32_t)kWinB / 16u;
         auto chunk_lim = [&](uint32_t x) {  // x: in_off at the literal chunk's end
             x = min(x, a.in_cap) + a.in_mis;
             return min(last16, x ? (x - 1u) >> 4 : 0u);
         };
-        uint32_t clim = kCut ? chunk_lim(gend0) : last16;
+        uint32_t clim = chunk_lim(gend0);
         auto prefetch = [&](uint32_t c, uint32_t e, uint32_t base16) {
             const uint32_t cnt = min(128u, e - c);  // >= 1
 #pragma unroll
@@ -450,7 +404,6 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
         uint32_t cur = cur0, ce = ce0;  // the first chunk (above)
         given = true;
         uint32_t gin = 0, gout = 0;
-        uint32_t sens[4] = {0u, 1u, 2u, 3u};  // diagnostic mode 6 only
         if (cur < ce) {
             gin = gin0 + a.in_mis;
             gout = (kCompact ? ulay(cur, gin0) : gout0) + a.out_mis;
@@ -501,7 +454,8 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
             }
             ri0 = ri1 = 0xFFFFFFFFu;
         };
-        // (v40, HPK_FLUSH_SPLIT) the same write-back in two parts. flush_read: every lane's F image chunks and
+        // (v40) the same write-back in two parts, the region form's at every fill (the compacted form has no
+        // write-back, and the cold exits use flush()). flush_read: every lane's F image chunks and
         // its byte of a partial end chunk into registers, unconditionally and in straight-line code (a lane
         // past the span reads the image's last chunk, within the image, and never stores it), so the F + 1 LDS
         // reads are in flight together and what is issued after them (the sort's round trips) runs under their
@@ -608,7 +562,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                     np = jn[1];
                     second = false;
                 }
-                while (HPK_CW_LANE_DIAG != 2 && __any(tp < np)) {
+                while (__any(tp < np)) {
                     if (tp < np) {
                         if (np >= 16u) {  // a 16-byte piece at t (the last one ending at n)
                             const uint32_t t = min(tp, np - 16u), u = sp + t;
@@ -621,12 +575,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                             v.y = __builtin_amdgcn_alignbyte(A[2], A[1], s3);
                             v.z = __builtin_amdgcn_alignbyte(A[3], A[2], s3);
                             v.w = __builtin_amdgcn_alignbyte(A[4], A[3], s3);
-                            if (HPK_CW_LANE_DIAG == 3)
-                                *reinterpret_cast<u32x4u*>(a.out_base + ((dp + t) & ~15u)) = v;
-                            else if (HPK_CW_LANE_DIAG == 4)
-                                asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-                            else
-                                *reinterpret_cast<u32x4u*>(a.out_base + dp + t) = v;
+                            *reinterpret_cast<u32x4u*>(a.out_base + dp + t) = v;
                             tp += 16u;
                         } else if (np >= 4u) {  // dwords at 0, 4, 8 and the last one ending at n
                             u32u* const g = reinterpret_cast<u32u*>(a.out_base + dp);
@@ -731,7 +680,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 cur += 1;
                 if (cur == ce) {  // the next chunk
                     claim(cur, ce);
-                    if (kCut && cur < ce) clim = chunk_lim(a.in_off[ce]);
+                    if (cur < ce) clim = chunk_lim(a.in_off[ce]);
                 }
                 if (cur < ce) {
                     gin = a.in_off[cur] + a.in_mis;
@@ -753,7 +702,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 if (cur_n < ce_n) {
                     gin_n = a.in_off[cur_n] + a.in_mis;
                     gout_n = oof(cur_n) + a.out_mis;
-                    if (kCut) clim = chunk_lim(a.in_off[ce_n]);
+                    clim = chunk_lim(a.in_off[ce_n]);
                 }
             }
             // 2. the window, big-endian dwords: bit P of the stream is bit 31 - P % 32 of dword P / 32
@@ -770,20 +719,20 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                                             __builtin_bswap32(c.w));
                 }
             };
-            // 3. the previous fill's write-back: its image is read out (kSplit: the reads are issued, which is
-            // enough, since a wave's LDS operations execute in order) before this fill's queue lands there
-            constexpr bool kSplit = HPK_FLUSH_SPLIT != 0 && !kCompact, kPfEarly = HPK_PF_EARLY != 0;
+            // 3. the previous fill's write-back: its image is read out (the reads are issued, which is enough,
+            // since a wave's LDS operations execute in order) before this fill's queue lands there
+            constexpr bool kSplit = !kCompact;
             stage();
             stamp(4);
-            if (!kSplit && pk) flush();
+            if (!kSplit && pk) flush();  // (the compacted form stores a fill when it is decoded: pk stays 0)
             if (kSplit) flush_read();
             asm volatile("" ::: "memory");  // (the image's reads stay ahead of the sort's stores)
             stamp(2);
-            // 4. queue, longest first (kRank 0: a counting sort over 32 length classes of 2 bytes, 996-1015
-            // us on config 5 against 1121-1175 us for the ballot ranks, r3h/r3j), long literals listed
-            // for the long-literal phase instead. (Measured and not taken, v40: the counts and the queue in the
-            // window, which is dead until it is staged, so that the sort needs no image read-out before it:
-            // within the spread of this order)
+            // 4. queue, longest first by a counting sort over 32 length classes of 2 bytes, long literals listed
+            // for the long-literal phase instead. (Measured and not taken: ranks from ballots, no LDS round trip,
+            // 1121-1175 us on config 5 against 996-1015; v40: the counts and the queue in the window, which is
+            // dead until it is staged, so that the sort needs no image read-out before it: within the spread of
+            // this order. DESIGN.md §4.0.)
             static_assert(256 + 128 * 8 <= G::kImg, "the sort's counts and queue in the image");
             bool qd[2];
             uint32_t key[2];
@@ -793,11 +742,11 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 const bool lng = nbytes >= a.long_min && !(ey[r] & kQ7Byte);
                 if (fits[r] && lng) leave(cur + lane + 64u * r, nbytes);
                 qd[r] = fits[r] && !lng;
-                key[r] = kRank == 1 ? min(nbytes >> 2, 15u) : min(nbytes >> 1, 31u);
+                key[r] = min(nbytes >> 1, 31u);
             }
             uint32_t rank0 = 0, rank1 = 0, kq = 0;
             uint2* const q = reinterpret_cast<uint2*>(s_img + 256);  // 128 entries, in the image
-            if (kRank == 0) {  // counting sort: class counts by LDS atomics, bases by a wave scan
+            {  // class counts by LDS atomics, bases by a wave scan
                 uint32_t* const hist = reinterpret_cast<uint32_t*>(s_img);  // 32 counts, then 32 bases
                 if (lane < 32) hist[lane] = 0;
                 const uint32_t pa = qd[0] ? atomicAdd(&hist[31u - key[0]], 1u) : 0u;
@@ -819,17 +768,6 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 rank0 = hist[32 + 31 - key[0]] + pa;
                 rank1 = hist[32 + 31 - key[1]] + pb;
             }
-#pragma unroll
-            for (int c = (kRank == 1 ? 15 : 31); kRank != 0 && c >= 0; --c) {
-                const bool h0 = qd[0] && key[0] == (uint32_t)c, h1 = qd[1] && key[1] == (uint32_t)c;
-                const uint64_t m0 = __ballot(h0), m1 = __ballot(h1);
-                const uint32_t p0 = (uint32_t)__popcll(m0);
-                const uint32_t b0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
-                const uint32_t b1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
-                rank0 = h0 ? kq + b0 : rank0;
-                rank1 = h1 ? kq + p0 + b1 : rank1;
-                kq += p0 + (uint32_t)__popcll(m1);
-            }
             if (qd[0]) q[rank0] = make_uint2(ex[0], ey[0]);
             if (qd[1]) q[rank1] = make_uint2(ex[1], ey[1]);
             // 5. the snake's two queue entries per lane (read before the image is decoded over), and
@@ -844,17 +782,17 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
             // 6. the next fill's offsets and window, in flight while this one decodes. Issued
             // unconditionally (past the last chunk: this fill's again, never used): under a branch the
             // registers' old and new values met in copies, and a copy waits for its load (vmcnt(0)
-            // right after the loads: every fill waited for the next fill's offsets)
+            // right after the loads: every fill waited for the next fill's offsets). Since v40 ahead of the
+            // write-back's stores.
             auto prefetch_next = [&]() {
                 const bool more = cur_n < ce_n;
                 prefetch(more ? cur_n : cur, more ? ce_n : cur + k, (more ? gin_n : gin) & ~15u);
             };
-            if (kPfEarly) prefetch_next();
+            prefetch_next();
             stamp(5);
             // (the write-back's stores: the sort above ran under their LDS reads)
             if (kSplit && pk) flush_store();
             stamp(2);
-            if (!kPfEarly) prefetch_next();
             // 7. lane walks: slots t1 then t2
             Lit12 L, N;
             auto load = [&](Lit12& T, const uint2 e, uint32_t tt) {
@@ -871,7 +809,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 lit12_load(T, wl32);
             };
             load(L, e1, t1);  // (the second literal is loaded when it starts, v28)
-            uint32_t sX = 0, sO = 0, sSt = 0;
+            uint32_t sO = 0, sSt = 0;
             bool s1 = false;
             stamp(5);
             uint32_t Lend = 0;  // the second walk's output end (bytes, image-relative)
@@ -879,38 +817,21 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 // v27: body steps (lit12_body, no fit tests) while a literal has >= kBodyMin bits left,
                 // slot t1's body then slot t2's; then the two literals' last bits (v38: the masked
                 // tail, the checked steps of v27 only for its slow lanes). A lane's first literal waits between the
-                // two phases as (aX, aO, aSt). (Measured and not taken, round 5: accumulated dword
-                // stores, dword ORs, both bodies or both tails in one block)
-                constexpr bool kRound = HPK_BODY_ROUND != 0 && kMode != 6;  // (mode 6 adds its VALU to the v40 steps)
+                // two phases as (aX, aO, aSt, aN). (Measured and not taken, round 5: accumulated dword
+                // stores, dword ORs, both bodies or both tails in one block; v41: a step at a time, each under its
+                // own `if (body)`, or long codes inline in the round)
                 bool body = L.Eb - L.X >= body_min<kTab>();
                 uint32_t aX = L.X, aO = L.o, aSt = L.st;
                 bool aAct = L.act, onA = true;
                 // (every lane switches exactly once before the loop ends, a lane with no second literal to an
                 // empty slot: the loop ends when no lane is in a body, and a lane not in a body switches first)
-                constexpr bool kSaved = HPK_TAIL_SAVED != 0 && HPK_TAIL_MASKED != 0, kCarry = HPK_ST_CARRY != 0;
-                uint32_t aN = 0;  // kSaved: the first literal's tail word (Tail12::n), made from its dword pair
+                uint32_t aN = 0;  // the first literal's tail word (Tail12::n), made from its dword pair
                 for (;;) {
                     dg_add(9, 1u);
-                    if (kRound)  // v41: the round's steps nested, one narrowing of exec each (lit12_round)
-                        lit12_round<kStore, kTab, HPK_BODY_UNROLL, HPK_BODY_ROUND - 1, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(
-                            L, wl32, s_lut, s_lo, ol8, body, [](bool p) { return __any(p) != 0; });
-#pragma unroll
-                    for (int s = 0; !kRound && s < HPK_BODY_UNROLL; ++s) {
-                        if (body)
-                            lit12_body<kStore, kTab, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(L, wl32, s_lut, s_lo, ol8,
-                                                                                                   body);
-                        if (kMode == 6) {  // sensitivity diagnostic: 16 independent VALU per step (4 chains of
-                                           // 4) off the walk's dependency chain; the kernel's response says
-                                           // whether VALU issue binds
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[0]) : "v"(L.X));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[1]) : "v"(L.o));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[2]) : "v"(L.Eb));
-                                asm volatile("v_xor_b32 %0, %0, %1" : "+v"(sens[3]) : "v"(L.d1));
-                            }
-                        }
-                    }
+                    // v41: the round's kBodyUnroll steps nested, one narrowing of exec each, long codes once a
+                    // round and a parked lane staying in the round (lit12_round, kDefer 2)
+                    lit12_round<kStore, kTab, kBodyUnroll, 2, (kMode >= 8 && kMode <= 10) ? kMode - 7 : 0>(
+                        L, wl32, s_lut, s_lo, ol8, body, [](bool p) { return __any(p) != 0; });
                     if (__any(!body)) {
                         const bool sw = !body & onA;
                         if (sw) {  // the first literal's body is done: it waits, the second one starts (its
@@ -919,7 +840,7 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                             aO = L.o;
                             aSt = L.st;
                             aAct = L.act;
-                            if (kSaved) aN = tail12_word(L);
+                            aN = tail12_word(L);
                             load(L, e2, t2);
                             onA = false;
                             body = L.Eb - L.X >= body_min<kTab>();
@@ -939,49 +860,43 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 L.o0 = obase + ((e1.y >> 12) & 0x1FFFFu);
                 L.idx = e1.y & 0xFFFu;
                 if (aSt != HPK_OK) L.Eb = L.X;  // ended in its body (EOS / padding): no tail
-                if (!kSaved) lit12_load(L, wl32);
                 L.more = L.Eb - L.X >= 5u;  // (fewer bits than the shortest code: ended)
                 N.more = N.Eb - N.X >= 5u;
                 stamp(12);
                 bool slowL = true;  // the first literal's walk did not end in the masked tail
-                if (HPK_TAIL_MASKED) {
-                    // v38: the masked tail (lit12_tail) on both literals, the two chains' lookups in turn
-                    // (they are independent and neither waits); a lane it leaves as slow (a 13..28-bit
-                    // code in the tail, or a code cut by the literal's end) keeps its state and takes the
-                    // checked steps below, the other lanes' walks have ended
-                    Tail12 TL, TN;
-                    if (kSaved)
-                        tail12_begin_saved(TL, aN, L.Eb - L.X, L.o);
-                    else
-                        tail12_begin(TL, L);
-                    tail12_begin(TN, N);
+                // v38: the masked tail (lit12_tail) on both literals, the two chains' lookups in turn
+                // (they are independent and neither waits); a lane it leaves as slow (a 13..28-bit
+                // code in the tail, or a code cut by the literal's end) keeps its state and takes the
+                // checked steps below, the other lanes' walks have ended. v42: the first literal's tail starts
+                // from its saved word (no lane reloads its window dwords for it).
+                Tail12 TL, TN;
+                tail12_begin_saved(TL, aN, L.Eb - L.X, L.o);
+                tail12_begin(TN, N);
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        tail12_look<kStore, kTab>(TL, s_lut, ol8, dmy);
-                        tail12_look<kStore, kTab>(TN, s_lut, ol8, dmy);
-                    }
-                    slowL = tail12_end<kTab>(TL, L);
-                    L.more &= slowL;
-                    N.more &= tail12_end<kTab>(TN, N);
+                for (int s = 0; s < 4; ++s) {
+                    tail12_look<kStore, kTab>(TL, s_lut, ol8, dmy);
+                    tail12_look<kStore, kTab>(TN, s_lut, ol8, dmy);
                 }
+                slowL = tail12_end<kTab>(TL, L);
+                L.more &= slowL;
+                N.more &= tail12_end<kTab>(TN, N);
                 // a slow first literal (a 14..30-bit code in its tail, a code cut by its end, or residual bits
                 // that complete a code with the ones past the end: 2.7 % of config 5's fills hold one) takes
                 // its dwords now, for the checked steps and for its status
-                if (kSaved && __any(slowL)) {
+                if (__any(slowL)) {
                     if (slowL) lit12_load(L, wl32);
                 }
                 while (__any(L.more | N.more)) {
                     if (L.more) lit12_step<kStore, true, kTab, true>(L, wl32, s_lut, s_lo, ol8, dmy);
                     if (N.more) lit12_step<kStore, true, kTab, true>(N, wl32, s_lut, s_lo, ol8, dmy);
                 }
-                // kCarry: every other lane's st is already final (tail12_end: the residual bits' status unless
+                // v42: every other lane's st is already final (tail12_end: the residual bits' status unless
                 // the body set one); a slow lane's comes from the window at its stop (from its dword pair, as the
                 // second slot's: 8 bytes of scratch in the region instantiation)
-                if (kCarry && __any(slowL)) {
+                if (__any(slowL)) {
                     if (slowL && L.st == HPK_OK) L.st = residual_status(L.Eb - L.X, win_at(wl32, L.X - 31u));
                 }
                 // results: the first slot's end state saved, the second in L
-                sX = L.X;
                 sO = L.o;
                 sSt = L.st;
                 s1 = L.act;
@@ -989,13 +904,10 @@ __global__ __launch_bounds__(1024) void hpk_decode_wave(DecodeArgs a) {
                 Lend = L.o;
             }
             stamp(6);
-            if (kMode == 6 && (sens[0] ^ sens[1] ^ sens[2] ^ sens[3]) == 0x5EB51u)
-                a.status[0] = 9u;  // (never: keeps the diagnostic work alive)
-            // results: the first slot's from its saved end state, the second's from the walk
+            // results: the first slot's from its saved end state (its status the one its tail computed), the
+            // second's from the walk
             {
-                const uint32_t Eb = wbits + (e1.x & 0xFFFFu) * 8u + 31u + (e1.x >> 16) * 8u;
-                const uint32_t st = HPK_ST_CARRY != 0 || sSt != HPK_OK ? sSt : residual_status(Eb - sX, win_at(wl32, sX - 31u));
-                rv0 = (sO - obase - ((e1.y >> 12) & 0x1FFFFu)) | (st << 24);
+                rv0 = (sO - obase - ((e1.y >> 12) & 0x1FFFFu)) | (sSt << 24);
                 ri0 = s1 ? e1.y & 0xFFFu : 0xFFFFFFFFu;
                 rv1 = (Lend - L.o0) | (lit12_status(L) << 24);
                 ri1 = L.act ? L.idx : 0xFFFFFFFFu;

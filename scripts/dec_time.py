@@ -62,7 +62,7 @@ def main():
                       "lib": os.path.basename(os.environ.get("HPK_LIB", "libhpk.so")),
                       "debug_mode": os.environ.get("HPK_DEBUG_MODE", "0"),
                       "kernel": os.environ.get("HPK_DECODE_KERNEL", "auto"),
-                      "wave_variant": os.environ.get("HPK_WAVE_VARIANT"), "compact": compact,
+                      "compact": compact,
                       "written_bytes": int(doff[-1].item()) & 0xFFFFFFFF if compact else None}), flush=True)
 
 

@@ -199,7 +199,7 @@ def main():
     ap.add_argument("--image", type=int, default=IMG, help="usable image bytes per wave")
     ap.add_argument("--lut-bits", type=int, default=LUT_BITS, choices=range(12, 17),
                     help="index bits of the two-symbol table; the body's least bits left are 2 * bits + 5")
-    ap.add_argument("--unroll", type=int, default=4, help="body step slots per loop round (HPK_BODY_UNROLL)")
+    ap.add_argument("--unroll", type=int, default=4, help="body step slots per loop round (kBodyUnroll)")
     ap.add_argument("--key", choices=["bytes2", "bytes4", "steps", "none"], default="bytes2",
                     help="longest-first sort key: 32 classes of 2 encoded bytes (the kernel's), 16 of 4, the body "
                          "steps themselves (an oracle), or arrival order")

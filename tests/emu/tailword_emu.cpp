@@ -1,4 +1,4 @@
-// Host replay of the wave kernel's fill trim (hpk_wave.h, HPK_TAIL_SAVED and HPK_ST_CARRY) with the REAL functions
+// Host replay of the wave kernel's fill trim (hpk_wave.h: the saved tail word and the carried status) with the REAL functions
 // of loona_amd/csrc (hpk_walk.h as it is; tests/emu/shim.h stands in for the HIP builtins), under table kind 4:
 //   a. tails alone: every bit pattern of 0..16 bits (0..13 bits at every X % 32, 14..16 at four), random patterns
 //      of 17..30 bits, all ones and all zeros, behind random window bits and followed by random bits:

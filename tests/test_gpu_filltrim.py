@@ -1,4 +1,4 @@
-"""Placed cases for the wave fills' trimmed lane-loop surroundings (hpk_wave.h, HPK_TAIL_SAVED and HPK_ST_CARRY): a
+"""Placed cases for the wave fills' trimmed lane-loop surroundings (hpk_wave.h, the fill trim of v42): a
 lane's first literal starts its masked tail from the word saved where its body ended, and its status is the one its
 tail computed; only the tail's slow lanes read the window again. GPU: the wave kernel through the C ABI against the
 pinned oracle, bit for bit, in the region, the compacted and the packed form. CPU (no GPU needed,

@@ -1,4 +1,4 @@
-"""The wave fills' trimmed tail entry (hpk_wave.h, HPK_TAIL_SAVED and HPK_ST_CARRY) run on the CPU (no GPU needed).
+"""The wave fills' trimmed tail entry (hpk_wave.h: the saved tail word and the carried status) run on the CPU (no GPU needed).
 
 tests/emu/tailword_emu.cpp includes the REAL hpk_walk.h (tests/emu/shim.h stands in for the HIP builtins), as
 tests/test_walk13_emulation.py does, and checks under table kind 4:
