@@ -729,6 +729,16 @@ uint64_t hpk_test_small_calls(const hpk_ctx* ctx);
  * shader-clock cycles: offsets loaded, staged, walked, stored. out10 is a buffer of 10 values: the six
  * request stamps, then the four of the literal. */
 int hpk_test_small_stamps(const hpk_ctx* ctx, uint32_t* out10);
+/* Testing only: the geometry of the small-call mode's persistent kernel: the encoded bytes up to which a literal
+ * is staged in LDS (longer ones are walked from global memory), the 16-byte chunks of a lane's input slot, the
+ * dwords of a lane's output slot, and the threads of a workgroup. A pure host function (no device needed). The
+ * tests place their edge cases relative to these. */
+int hpk_test_persist_geometry(uint32_t* slot_max, uint32_t* slot_chunks, uint32_t* out_dwords, uint32_t* threads);
+/* Testing only: stop the small-call mode's persistent kernel if it runs and make `v` the last request number
+ * issued, so that the next small call issues the number after it (the numbers wrap at 2^32 and skip
+ * 0xFFFFFFFF, the kernel's exit command, and 0). v = 0xFFFFFFFF, or a context whose mode was never turned on, is
+ * HPK_E_INVAL. */
+int hpk_test_small_set_request(hpk_ctx* ctx, uint32_t v);
 /* Testing only: the block scan's geometry (hpk_scan_blocks): the blocks a workgroup of either pass walks, one
  * per lane. The tests place their block counts relative to it. */
 int hpk_test_blkscan_geometry(uint32_t* wg_blocks);

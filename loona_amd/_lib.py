@@ -122,6 +122,8 @@ EXPORTS = (
     "hpk_test_decode_geometry",
     "hpk_test_small_calls",
     "hpk_test_small_stamps",
+    "hpk_test_persist_geometry",
+    "hpk_test_small_set_request",
     "hpk_test_blkscan_geometry",
     "hpk_ctx_set_decode_kernel",
     "hpk_ctx_set_small_mode",
@@ -331,6 +333,12 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "hpk_test_small_calls"):
             L.hpk_test_small_calls.argtypes = [ctypes.c_void_p]
             L.hpk_test_small_calls.restype = ctypes.c_uint64
+        if hasattr(L, "hpk_test_persist_geometry"):
+            L.hpk_test_persist_geometry.argtypes = [c_u32p] * 4
+            L.hpk_test_persist_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_test_small_set_request"):
+            L.hpk_test_small_set_request.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.hpk_test_small_set_request.restype = ctypes.c_int
         if hasattr(L, "hpk_test_bound_scan"):
             L.hpk_test_bound_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
             L.hpk_test_bound_scan.restype = ctypes.c_int

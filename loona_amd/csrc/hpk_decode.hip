@@ -172,7 +172,26 @@ static int persist_launch(hpk_ctx* c, uint32_t base) {
 
 int hpk_persist_start(hpk_ctx* c) { return persist_launch(c, c->sm_req); }
 
+// The request number after k. Two values are never issued: kPersistExit, which the kernel reads as its exit
+// command (it would leave, be launched again, read the same request and leave again until the call's deadline),
+// and 0, the declined word's value after a launch (the request's last workgroup would report a good batch as
+// declined). A launch's base is the last number issued (or 0 before the first), so it is never kPersistExit.
+static uint32_t persist_next(uint32_t k) {
+    do k += 1u;
+    while (k == kPersistExit || k == 0u);
+    return k;
+}
+
 extern "C" uint64_t hpk_test_small_calls(const hpk_ctx* c) { return c ? c->sm_calls : 0u; }
+
+extern "C" int hpk_test_persist_geometry(uint32_t* slot_max, uint32_t* slot_chunks, uint32_t* out_dwords, uint32_t* threads) {
+    if (!slot_max || !slot_chunks || !out_dwords || !threads) return HPK_E_INVAL;
+    *slot_max = kPersistSlotMax;
+    *slot_chunks = kPersistSlotChunks;
+    *out_dwords = kPersistOutDw;
+    *threads = (uint32_t)kPersistThreads;
+    return HPK_E_OK;
+}
 
 extern "C" int hpk_test_small_stamps(const hpk_ctx* c, uint32_t* out10) {
     if (!c || !c->h_sm || !out10) return HPK_E_INVAL;
@@ -188,6 +207,14 @@ int hpk_persist_stop(hpk_ctx* c) {
     __atomic_store_n(&h->stop, 1u, __ATOMIC_RELEASE);
     HIP_TRY(hipStreamSynchronize(c->sm_stream));
     c->sm_launched = false;
+    return HPK_E_OK;
+}
+
+extern "C" int hpk_test_small_set_request(hpk_ctx* c, uint32_t v) {
+    if (!c || !c->h_sm || v == kPersistExit) return HPK_E_INVAL;  // (never issued, so never a launch's base either)
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = hpk_persist_stop(c)) return rc;
+    c->sm_req = v;  // (the next call launches the kernel with this base)
     return HPK_E_OK;
 }
 
@@ -213,12 +240,13 @@ int hpk_persist_call(hpk_ctx* c, const hpk_batch& b, bool* handled) {
     h->out_mis = out.mis;
     h->in_cap = b.in_cap;
     h->out_cap = b.out_cap;
-    const uint32_t k = ++c->sm_req;
+    const uint32_t prev = c->sm_req, k = persist_next(prev);
+    c->sm_req = k;
     __atomic_store_n(&h->req, k, __ATOMIC_RELEASE);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 0; __atomic_load_n(&h->done, __ATOMIC_ACQUIRE) != k; ++spins) {
         if (__atomic_load_n(&h->alive, __ATOMIC_ACQUIRE) == 0u) {  // it went idle just before the request
-            if (int rc = persist_launch(c, k - 1u)) return rc;
+            if (int rc = persist_launch(c, prev)) return rc;
         }
         __builtin_ia32_pause();
         if ((spins & 4095u) == 4095u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))

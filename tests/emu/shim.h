@@ -13,3 +13,8 @@ static inline uint32_t __builtin_amdgcn_alignbit(uint32_t a, uint32_t b, uint32_
 }
 static inline uint32_t __clz(uint32_t x){ return x? __builtin_clz(x):32; }
 struct uint4 { uint32_t x, y, z, w; };
+// hpk_persist_lit.h: global pointers are plain ones, the 4-dword vector, the byte swap, the shader clock
+#define HPK_GAS
+struct u32x4 { uint32_t x, y, z, w; };
+static inline uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }
+static inline uint64_t __builtin_amdgcn_s_memtime() { return 0; }
