@@ -656,6 +656,7 @@ typedef struct hpk_henc hpk_henc;
 hpk_henc* hpk_henc_create(int huffman);                           /* Encoder::new(): max table 4096 */
 void hpk_henc_destroy(hpk_henc* enc);
 int hpk_henc_set_max_table_size(hpk_henc* enc, size_t max_size); /* encoder.rs:193-197 */
+int hpk_henc_table_size(const hpk_henc* enc, size_t* size, size_t* entries, size_t* max_size); /* as hpk_hdec_table_size */
 /* Encoder::encode (encoder.rs:210-234) of n headers: header j's name is
  * fields[field_off[2j] .. field_off[2j+1]) and its value fields[field_off[2j+1] .. field_off[2j+2]).
  * Writes the block into out[0 .. cap) and its length to *out_len. Returns HPK_E_OK; HPK_E_NOSPACE
@@ -665,7 +666,7 @@ int hpk_henc_encode(hpk_henc* enc, const uint8_t* fields, const uint32_t* field_
 
 /* Many responses' header blocks at once: block b encodes headers [hdr_off[b], hdr_off[b+1]) (header j
  * as in hpk_henc_encode) with encoder encs[b]; the blocks of one encoder are encoded in list order.
- * The table logic runs on the host. With a ctx and at least one non-empty string of a Huffman-coding
+ * The table logic runs on the host (hpk_ctx_set_block_plan moves it to the device, opt-in). With a ctx and at least one non-empty string of a Huffman-coding
  * encoder, every representation of every block goes through ONE hpk_encode_strings_packed call on ctx
  * (HPK_PTR_HOST): octets the host has made final as HPK_STR_VERBATIM, a string as HPK_STR_AUTO if its
  * encoder Huffman-codes, else HPK_STR_RAW, and the call's output is the blocks end to end. Otherwise
@@ -687,6 +688,112 @@ void hpk_henc_out_free(hpk_henc_out* out);
  * Testing only: the calling thread's next n Huffman batches inside hpk_henc_encode_blocks fail
  * with HPK_E_DEVICE (n = 0 clears it), so that guarantee can be checked without a device fault. */
 void hpk_test_fail_batches(int n);
+
+/* ---- HPACK header blocks: the encoder's table half on the device ---------------------------
+ * hpk_plan_blocks is the batch form of Encoder::encode (crates/loona-hpack/src/encoder.rs:210-264) without the
+ * string coding, the mirror of hpk_apply_blocks: for many encoders at once, in order per encoder, each header gets
+ * the representation the reference's single strategy picks (HeaderTable::find_header, crates/loona-hpack/src/
+ * lib.rs:261-288), the table is updated (add_header / consolidate_table, lib.rs:108-142), and the header is written
+ * out as up to three items that hpk_pack_batch and hpk_encode_strings_packed take as they stand.
+ * The arena. The plan reads string bytes, so there is ONE device blob `arena` of arena_cap bytes (above
+ * HPK_MAX_OFFSET: HPK_E_INVAL): the static text (hpk_static_table) at static_base; the call's names and values end
+ * to end at fields_base, header j's name arena[fields_base + field_off[2j] .. fields_base + field_off[2j+1]) and its
+ * value the next span (hpk_henc_encode's layout; field_off has 2 hdrs_cap + 1 entries); the prefix area at
+ * prefix_base, 4 bytes per header, the only part of the arena the call writes (prefix_base and arena + prefix_base
+ * multiples of 4, prefix_base + 4 hdrs_cap within arena_cap, static_base + the static text within arena_cap: else
+ * HPK_E_INVAL); and the bytes of the tables carried in wherever their tab_ent records say. Every reference is a
+ * (u32 offset, u32 length) pair into the arena; a table entry is an hpk_header, exactly as in hpk_apply_blocks.
+ * Encoders. Encoder e plans blocks enc_blk[enc_blk_off[e] .. enc_blk_off[e+1]) in that order; block b is headers
+ * [hdr_off[b], hdr_off[b+1]). The lists may interleave in any way, and a block belongs to at most one list.
+ * Encoder e works against tabs[e], an hpk_dtab as hpk_apply_blocks takes it: max_allowed is ignored; size must be the sum of name + value + 32
+ * over the count entries carried in (the call trusts it: a size that understates them comes back as a wrong table,
+ * though nothing outside the stated sizes is touched); count, size,
+ * max_size and the entries come back in the same layout (an inserted entry refers to the header's own bytes in the
+ * fields region); applied is the number of blocks planned. enc_flags[e] bit 0: the encoder Huffman-codes, its
+ * strings get HPK_STR_AUTO, otherwise HPK_STR_RAW.
+ * Per header. find_header runs over the static, then the dynamic entries, newest first: the lowest index whose name
+ * and value both match, else the highest index whose name matches (the reference's last name match: ":method PUT"
+ * gives 3). Then HPK_PLAN_INDEXED: the index as a 7-bit-prefix integer with 0x80. HPK_PLAN_NAME_INDEXED: the index
+ * as a 4-bit-prefix integer with 0x00, then the value string; the table is not touched. HPK_PLAN_NEW_NAME: 0x40, the
+ * name string, the value string, then add_header: an entry above max_size empties the table and adds nothing; sizes
+ * are summed in 64 bits.
+ * Outputs. reps[j] is header j's hpk_hrep. Each header has three item slots, 3j to 3j+2 of item_off / item_len /
+ * item_policy (3 hdrs_cap entries each): slot 0 is the prefix octets, written at arena[prefix_base + 4j ..) as one
+ * dword, policy HPK_STR_VERBATIM (3 octets at most for any index the ring allows); then the strings the kind needs,
+ * with the encoder's policy; an unused slot has length 0 under HPK_STR_VERBATIM and so emits nothing. A header emits
+ * at most three items, so 3 hdrs_cap is the capacity that always suffices: no count pass and no scan. With the items
+ * packed (hpk_pack_batch: arena, item_off, item_len) and coded (hpk_encode_strings_packed with item_policy), block
+ * b's bytes are out_off[3 hdr_off[b]] .. out_off[3 hdr_off[b+1]] of the strings call. Headers of a block in no list,
+ * of a deferred or of a void encoder keep the defaults the first pass writes for all hdrs_cap headers: kind
+ * HPK_PLAN_NONE and three empty verbatim slots. nencs == 0 or nblocks == 0 only writes the defaults.
+ * Deferral, hpk_apply_blocks' rule: with lim = min(ring_entries, tabs[e].cap) (hpk_test_blkplan_geometry), every
+ * block of an encoder is deferred when its max_size exceeds 32 * lim or its count lim at the call's start: applied =
+ * 0, the table untouched.
+ * Bad inputs. An encoder is void (applied = 0, the table untouched, the sticky flag set: a synchronous call returns
+ * HPK_E_INVAL) when its ent + cap passes tab_ent_cap or its count its cap; when its list's offsets decrease or pass
+ * enc_blk_off[nencs]; when a listed block is >= nblocks; when a listed block's hdr_off decreases or passes hdrs_cap;
+ * when a listed header's field_off decreases or its fields_base + field_off passes arena_cap; or when a carried-in
+ * entry's name or value passes arena_cap. Nothing outside the stated sizes is read or written.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC (anything else is HPK_E_INVAL); reps and tab_ent 16-byte aligned
+ * (HPK_E_INVAL). On the context's stream; always the launch path. Scratch per stream: 8 bytes per header.
+ * How: two kernels (hpk_blkplan.hip). A default-and-hash pass, one lane per header: the defaults, and a 32-bit hash
+ * of the name and of the value into scratch (a string with bad offsets hashes to 0 and is not read). The plan
+ * kernel, one wave per encoder: the lane-parallel look for void inputs; the table in a ring of ring_entries records
+ * in LDS, an hpk_header and the two hashes each, the carried-in entries hashed once at load, one lane per entry;
+ * static entry `lane` in each lane's registers; per chunk of chunk_headers headers the lanes stage offsets and
+ * hashes and the headers are resolved in turn: the search runs in ascending groups of search_group entries, each
+ * lane testing one entry by name length, name hash, value length and value hash and confirming on the arena's
+ * bytes, a ballot giving the lowest whole match, which ends the search, and the highest name match so far. The hash
+ * only filters: every match is confirmed on bytes.
+ * Costs: one lane hashes or confirms a whole string, so a multi-KiB value holds its wave for that many byte loads; a
+ * call takes as long as its longest encoder; the strings call sees 3 hdrs_cap items, most of them empty. */
+typedef enum hpk_plan_kind { HPK_PLAN_NONE = 0, HPK_PLAN_INDEXED = 1, HPK_PLAN_NAME_INDEXED = 2,
+                             HPK_PLAN_NEW_NAME = 3 } hpk_plan_kind;
+typedef struct hpk_hrep {    /* one planned header; 16 bytes */
+    uint32_t index;          /* the table index of the representation (0 for HPK_PLAN_NEW_NAME and HPK_PLAN_NONE) */
+    uint8_t  kind;           /* hpk_plan_kind */
+    uint8_t  prefix_len;     /* octets of `prefix` in use (0 for HPK_PLAN_NONE) */
+    uint16_t reserved0;
+    uint8_t  prefix[4];      /* the representation's first octets: the dword at arena[prefix_base + 4j] */
+    uint32_t reserved1;
+} hpk_hrep;
+
+int hpk_plan_blocks(hpk_ctx* ctx,
+        uint8_t* arena, size_t arena_cap, uint32_t static_base, uint32_t fields_base, uint32_t prefix_base,
+        const uint32_t* field_off, const uint32_t* hdr_off, uint32_t nblocks, size_t hdrs_cap,
+        const uint32_t* enc_blk_off, const uint32_t* enc_blk, const uint8_t* enc_flags, uint32_t nencs,
+                                  /* encoder e's blocks, in connection order: enc_blk[enc_blk_off[e] .. enc_blk_off[e+1]) */
+        hpk_dtab* tabs, hpk_header* tab_ent, size_t tab_ent_cap,
+        hpk_hrep* reps, uint32_t* item_off, uint32_t* item_len, uint8_t* item_policy, int flags);
+/* Where hpk_henc_encode_blocks runs a context's table logic. HPK_BLOCK_PLAN_HOST (the default): on the host, as
+ * described at hpk_henc_encode_blocks. HPK_BLOCK_PLAN_DEVICE (opt-in; calls without a context are not affected)
+ * selects the whole device pipeline: the blocks are grouped by encoder with a counting pass; one arena goes up (the
+ * static text, every distinct encoder's live entries' bytes, the fields; the prefix area is reserved, not uploaded)
+ * with the hpk_dtab / hpk_header records, the lists and the offsets; hpk_plan_blocks' two kernels run; hpk_pack_batch's
+ * kernels gather the 3 nh items into a contiguous blob; hpk_encode_strings_packed's steps code them with the item
+ * policies; the tables, their final entries, the output offsets at the block boundaries and exactly the coded bytes
+ * come back. Every encoder's table is then rebuilt from its final entries' bytes in the host's own copy of the arena.
+ * Nothing is written to an encoder before everything is back, so a device failure (or hpk_test_fail_batches) on this
+ * path leaves every encoder as it was. If any encoder would be deferred (its max_size above 32 * ring_entries or its
+ * entries above ring_entries, which the host sees before any upload), if the arena or the items' bound would pass the
+ * u32 offset range, if no block has a header, or if an encoder came back not fully planned, the host path answers
+ * the whole call with its own checks. Results and encoder states equal the default path's byte for byte.
+ * Measurements: with HPK_HENC_TIMING set in the environment, every call on the device path waits for the stream
+ * after each pass and prints the passes' wall times to stderr (upload, plan, item gather, string coding, copies
+ * back); scripts/blocks_plan_time.py split collects them. */
+#define HPK_BLOCK_PLAN_HOST 0    /* the default */
+#define HPK_BLOCK_PLAN_DEVICE 1
+int hpk_ctx_set_block_plan(hpk_ctx* ctx, int kind);
+/* Testing only: how many hpk_henc_encode_blocks calls of this context the device-plan path has answered (its tables
+ * committed), so the tests can tell it from the host path, which answers by default and after a fallback. */
+uint64_t hpk_test_plan_calls(const hpk_ctx* ctx);
+/* Testing only: the block plan's geometry (hpk_plan_blocks): the records of an encoder's ring in LDS, the headers a
+ * wave stages at a time, the encoders per workgroup (one wave each) and the entries a search step tests. */
+int hpk_test_blkplan_geometry(uint32_t* ring_entries, uint32_t* chunk_headers, uint32_t* wg_encoders,
+                              uint32_t* search_group);
+/* Testing only: the plan kernels' hash of n strings, string i = blob[off[i] .. off[i+1]), into out (n entries). A
+ * pure host function. The tests use it to place collisions. */
+int hpk_test_blkplan_hash(const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t* out);
 /* Testing only: the compacted form's internal bound layout of n literals' device offsets in_off
  * (n + 1 entries) into device memory out (n + 1 entries): the exclusive sum mod 2^32 of
  * (floor(8 len / 5) + 3) & ~3, synchronously on the context's stream. */

@@ -48,6 +48,15 @@ HPK_BLOCK_APPLY_DEVICE = 1
 HPK_DTAB_NO_LIMIT = 0xFFFFFFFF
 HPK_BLK_DEFERRED = 10
 
+# hpk_ctx_set_block_plan (hpk.h)
+HPK_BLOCK_PLAN_HOST = 0
+HPK_BLOCK_PLAN_DEVICE = 1
+# hpk_plan_blocks (hpk.h): hpk_plan_kind
+HPK_PLAN_NONE = 0
+HPK_PLAN_INDEXED = 1
+HPK_PLAN_NAME_INDEXED = 2
+HPK_PLAN_NEW_NAME = 3
+
 # string-literal policies of hpk_encode_strings_packed (hpk.h)
 HPK_STR_AUTO = 0
 HPK_STR_RAW = 1
@@ -84,6 +93,11 @@ EXPORTS = (
     "hpk_static_table",
     "hpk_ctx_set_block_apply",
     "hpk_test_blkapply_geometry",
+    "hpk_plan_blocks",
+    "hpk_ctx_set_block_plan",
+    "hpk_test_plan_calls",
+    "hpk_test_blkplan_geometry",
+    "hpk_test_blkplan_hash",
     "hpk_decode_batch_cpu",
     "hpk_encode_batch_cpu",
     "hpk_host_register",
@@ -110,6 +124,7 @@ EXPORTS = (
     "hpk_henc_create",
     "hpk_henc_destroy",
     "hpk_henc_set_max_table_size",
+    "hpk_henc_table_size",
     "hpk_henc_encode",
     "hpk_henc_encode_blocks",
     "hpk_henc_out_free",
@@ -248,6 +263,23 @@ def lib() -> ctypes.CDLL:
             L.hpk_ctx_set_block_apply.restype = ctypes.c_int
             L.hpk_test_blkapply_geometry.argtypes = [c_u32p] * 3
             L.hpk_test_blkapply_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_plan_blocks"):  # (likewise: no block plan)
+            L.hpk_plan_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int]
+            L.hpk_plan_blocks.restype = ctypes.c_int
+            L.hpk_ctx_set_block_plan.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.hpk_ctx_set_block_plan.restype = ctypes.c_int
+            L.hpk_test_plan_calls.argtypes = [ctypes.c_void_p]
+            L.hpk_test_plan_calls.restype = ctypes.c_uint64
+            L.hpk_test_blkplan_geometry.argtypes = [c_u32p] * 4
+            L.hpk_test_blkplan_geometry.restype = ctypes.c_int
+            L.hpk_test_blkplan_hash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+            L.hpk_test_blkplan_hash.restype = ctypes.c_int
+            L.hpk_henc_table_size.argtypes = [ctypes.c_void_p, c_sizep, c_sizep, c_sizep]
+            L.hpk_henc_table_size.restype = ctypes.c_int
         for fn in batch_fns:
             fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

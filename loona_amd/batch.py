@@ -27,6 +27,9 @@ HEADER_DTYPE = np.dtype([("name_off", "<u4"), ("name_len", "<u4"), ("value_off",
 RESULT_DTYPE = np.dtype([("first_header", "<u4"), ("n_headers", "<u4"), ("error", "<i4"), ("detail", "<i4")])
 DTAB_DTYPE = np.dtype([("ent", "<u4"), ("cap", "<u4"), ("count", "<u4"), ("size", "<u4"), ("max_size", "<u4"),
                        ("max_allowed", "<u4"), ("applied", "<u4"), ("reserved", "<u4")])
+# hpk_hrep (hpk.h): one 16-byte record of plan_blocks
+HREP_DTYPE = np.dtype([("index", "<u4"), ("kind", "u1"), ("prefix_len", "u1"), ("reserved0", "<u2"), ("prefix", "u1", (4,)),
+                       ("reserved1", "<u4")])
 # hpk_field (hpk.h): one 16-byte record of scan_blocks
 FIELD_DTYPE = np.dtype([("index", "<u4"), ("str", "<u4"), ("kind", "u1"), ("nstr", "u1"), ("err", "u1"),
                         ("err_stage", "u1"), ("at", "<u4")])
@@ -760,6 +763,69 @@ class HuffmanCodec:
                                       ctypes.c_uint32(nd), pt, pe, ebytes // 16, ph, hbytes // 16, pr, flags)
         _lib.check(rc, "hpk_apply_blocks")
         return headers, results
+
+    BLOCK_PLANS = {"host": _lib.HPK_BLOCK_PLAN_HOST, "device": _lib.HPK_BLOCK_PLAN_DEVICE}
+
+    def set_block_plan(self, kind: str):
+        """'host' (the default) or 'device' (hpk_ctx_set_block_plan): where hpack.encode_blocks runs this codec's
+        table logic. 'device' selects the whole device pipeline: plan_blocks' kernels against the encoders' tables
+        carried to the device and back, pack's kernels over the items, encode_strings' steps. The same bytes and
+        encoder states; a call holding an encoder whose table the device's ring cannot hold is answered by the
+        host path."""
+        if kind not in self.BLOCK_PLANS:
+            raise ValueError(f"block plan {kind!r} not in {tuple(self.BLOCK_PLANS)}")
+        _lib.check(self._L.hpk_ctx_set_block_plan(self._h, self.BLOCK_PLANS[kind]), "hpk_ctx_set_block_plan")
+
+    def plan_blocks(self, arena, static_base, fields_base, prefix_base, field_off, hdr_off, enc_blk_off, enc_blk, enc_flags, tabs,
+                    tab_ent, reps=None, item_off=None, item_len=None, item_policy=None, sync=False):
+        """hpk_plan_blocks: torch cuda tensors -> (reps, item_off, item_len, item_policy); tabs, tab_ent and the
+        arena's prefix area are updated in place. The encoder's table half for many encoders at once: arena (uint8)
+        holds the static text (static_table()) at static_base, the headers' names and values end to end at
+        fields_base (header j's name arena[fields_base + field_off[2j] : fields_base + field_off[2j + 1]], its value
+        the next span; field_off has 2 * headers + 1 entries), 4 bytes per header at prefix_base for the
+        representations' first octets, and the bytes of the carried-in table entries wherever tab_ent says. Block b
+        is headers hdr_off[b] : hdr_off[b + 1]; encoder e plans blocks enc_blk[enc_blk_off[e] : enc_blk_off[e + 1]]
+        in order against tabs[e] (32-byte hpk_dtab records, DTAB_DTYPE; entries 16-byte hpk_header records,
+        HEADER_DTYPE, newest first); enc_flags[e] & 1: the encoder Huffman-codes. reps (uint8, 16 bytes per header,
+        HREP_DTYPE) gets each header's kind, index and prefix octets; items 3j .. 3j + 2 of item_off / item_len /
+        item_policy are header j's prefix octets and strings, pack()'s and encode_strings()' inputs as they stand.
+        tabs[e]['applied'] says how many of the encoder's blocks were planned (0: deferred to the host). With
+        sync=True bad inputs raise (HPK_E_INVAL)."""
+        import torch
+
+        dev = self.device
+        nh = (int(field_off.shape[0]) - 1) // 2
+        n = int(hdr_off.shape[0]) - 1
+        ne = int(enc_blk_off.shape[0]) - 1
+        if nh < 0 or n < 0 or ne < 0:
+            raise ValueError("field_off, hdr_off and enc_blk_off need at least one entry")
+        if reps is None:
+            reps = torch.empty(16 * max(nh, 1), dtype=torch.uint8, device=arena.device)[: 16 * nh]
+        if item_off is None:
+            item_off = torch.empty(max(3 * nh, 1), dtype=torch.int32, device=arena.device)
+        if item_len is None:
+            item_len = torch.empty(max(3 * nh, 1), dtype=torch.int32, device=arena.device)
+        if item_policy is None:
+            item_policy = torch.empty(max(3 * nh, 1), dtype=torch.uint8, device=arena.device)
+        pa, abytes = _arg(arena, "arena", ("uint8",), 0, dev)
+        pfo, _ = _arg(field_off, "field_off", _OFF_DTYPES, 2 * nh + 1, dev)
+        pho, _ = _arg(hdr_off, "hdr_off", _OFF_DTYPES, n + 1, dev)
+        peo, _ = _arg(enc_blk_off, "enc_blk_off", _OFF_DTYPES, ne + 1, dev)
+        peb, _ = _arg(enc_blk, "enc_blk", _OFF_DTYPES, 0, dev)
+        pef, _ = _arg(enc_flags, "enc_flags", ("uint8",), ne, dev)
+        pt, _ = _arg(tabs, "tabs", ("uint8",), 32 * ne, dev)
+        pe, ebytes = _arg(tab_ent, "tab_ent", ("uint8",), 0, dev)
+        pr, _ = _arg(reps, "reps", ("uint8",), 16 * nh, dev)
+        pio, _ = _arg(item_off, "item_off", _OFF_DTYPES, 3 * nh, dev)
+        pil, _ = _arg(item_len, "item_len", _OFF_DTYPES, 3 * nh, dev)
+        pip, _ = _arg(item_policy, "item_policy", ("uint8",), 3 * nh, dev)
+        self._follow()
+        flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        rc = self._L.hpk_plan_blocks(self._h, pa, abytes, ctypes.c_uint32(int(static_base)), ctypes.c_uint32(int(fields_base)),
+                                     ctypes.c_uint32(int(prefix_base)), pfo, pho, ctypes.c_uint32(n), nh, peo, peb, pef,
+                                     ctypes.c_uint32(ne), pt, pe, ebytes // 16, pr, pio, pil, pip, flags)
+        _lib.check(rc, "hpk_plan_blocks")
+        return reps, item_off, item_len, item_policy
 
 
 def static_table():

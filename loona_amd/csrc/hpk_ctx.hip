@@ -1,5 +1,6 @@
 // hpk_ctx.hip — device context and the batch entry points of the C ABI (include/hpk.h).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
 
@@ -8,7 +9,7 @@
 
 #include "hpk_device.h"
 
-#define HPK_VERSION "hpk 0.45 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block); block apply v1 (one wave per decoder: lane-parallel look and stage, records resolved in order against a ring in LDS)"
+#define HPK_VERSION "hpk 0.46 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block); block apply v1 (one wave per decoder: lane-parallel look and stage, records resolved in order against a ring in LDS); block plan v1 (a default-and-hash pass, then one wave per encoder: headers resolved in order against a hashed ring in LDS, 64 entries a search step, matches confirmed on bytes)"
 
 static thread_local std::string t_last_error;
 
@@ -176,7 +177,7 @@ extern "C" void hpk_ctx_destroy(hpk_ctx* c) {
     for (hpk_slot& s : c->slots) {
         if (s.ev_set) (void)hipEventSynchronize(s.ev);
         for (DevBuf* b : {&s.long_list, &s.cp_bound, &s.cp_tmp, &s.cp_cursor, &s.pk_scratch, &s.pk_bound, &s.pk_tmp, &s.str_stage, &s.sd_meta,
-                          &s.sd_hblob, &s.sd_stage, &s.bs_meta, &s.bs_stage, &s.bs_out, &s.ba_buf})
+                          &s.sd_hblob, &s.sd_stage, &s.bs_meta, &s.bs_stage, &s.bs_out, &s.ba_buf, &s.bp_hash, &s.bp_buf})
             (void)hipFree(b->p);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
@@ -252,6 +253,16 @@ extern "C" int hpk_ctx_set_block_apply(hpk_ctx* c, int kind) {
 }
 
 int hpk_ctx_block_apply(const hpk_ctx* c) { return c ? c->block_apply : HPK_BLOCK_APPLY_HOST; }
+
+extern "C" int hpk_ctx_set_block_plan(hpk_ctx* c, int kind) {
+    if (!c || (kind != HPK_BLOCK_PLAN_HOST && kind != HPK_BLOCK_PLAN_DEVICE)) return hpk_set_err_msg("bad block plan", HPK_E_INVAL);
+    c->block_plan = kind;
+    return HPK_E_OK;
+}
+
+int hpk_ctx_block_plan(const hpk_ctx* c) { return c ? c->block_plan : HPK_BLOCK_PLAN_HOST; }
+void hpk_ctx_plan_answered(hpk_ctx* c) { c->plan_calls += 1; }
+extern "C" uint64_t hpk_test_plan_calls(const hpk_ctx* c) { return c ? c->plan_calls : 0u; }
 
 extern "C" void* hpk_ctx_stream(hpk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
@@ -1077,6 +1088,134 @@ extern "C" int hpk_apply_blocks(hpk_ctx* c, const hpk_field* fields, const uint3
     HIP_TRY(hipMemcpyAsync(&total, field_off + nblocks, 4, hipMemcpyDeviceToHost, c->stream));
     if (int rc = call_end(c, flags)) return rc;
     if ((size_t)total > headers_cap) return hpk_set_err_msg("the field total passes headers_cap", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The header-block plan (include/hpk.h).
+extern "C" int hpk_plan_blocks(hpk_ctx* c, uint8_t* arena, size_t arena_cap, uint32_t static_base, uint32_t fields_base,
+                               uint32_t prefix_base, const uint32_t* field_off, const uint32_t* hdr_off, uint32_t nblocks,
+                               size_t hdrs_cap, const uint32_t* enc_blk_off, const uint32_t* enc_blk, const uint8_t* enc_flags,
+                               uint32_t nencs, hpk_dtab* tabs, hpk_header* tab_ent, size_t tab_ent_cap, hpk_hrep* reps,
+                               uint32_t* item_off, uint32_t* item_len, uint8_t* item_policy, int flags) {
+    if (!c) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (!(flags & HPK_PTR_DEVICE)) return hpk_set_err_msg("the block plan takes device pointers only", HPK_E_INVAL);
+    if (arena_cap > HPK_MAX_OFFSET) return hpk_set_err_msg("the arena passes HPK_MAX_OFFSET", HPK_E_INVAL);
+    if (nblocks >= 0x7FFFFFFFu || nencs >= 0x7FFFFFFFu || hdrs_cap >= 0x40000000u)
+        return hpk_set_err_msg("too many blocks or headers for the block plan", HPK_E_INVAL);
+    if ((((uintptr_t)reps | (uintptr_t)tab_ent) & 15u) != 0) return hpk_set_err_msg("reps and tab_ent must be 16-byte aligned", HPK_E_INVAL);
+    if ((prefix_base & 3u) || (((uintptr_t)arena + prefix_base) & 3u) || (uint64_t)prefix_base + 4u * (uint64_t)hdrs_cap > arena_cap)
+        return hpk_set_err_msg("the prefix area must be 4-byte aligned and inside the arena", HPK_E_INVAL);
+    size_t static_len = 0;
+    (void)hpk_static_table(nullptr, &static_len, nullptr);
+    if ((uint64_t)static_base + static_len > arena_cap) return hpk_set_err_msg("the static text must lie inside the arena", HPK_E_INVAL);
+    if (hdrs_cap && (!arena || !field_off || !reps || !item_off || !item_len || !item_policy))
+        return hpk_set_err_msg("null array", HPK_E_INVAL);
+    const bool plan = nencs && nblocks;
+    if (plan && (!arena || !hdr_off || !enc_blk_off || !enc_blk || !enc_flags || !tabs || (tab_ent_cap && !tab_ent)))
+        return hpk_set_err_msg("null array", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!hdrs_cap && !plan) return call_end(c, flags);
+    int rc;
+    if (plan && (rc = apply_static(c))) return rc;
+    hpk_slot* s = nullptr;
+    if ((rc = slot_acquire(c, &s)) || (rc = slot_reserve(c, s, {{&s->bp_hash, 8 * hdrs_cap + 8}}))) return rc;
+    if ((rc = hpk_launch_blkplan(c, arena, (uint32_t)arena_cap, static_base, fields_base, prefix_base, field_off, hdr_off, nblocks,
+                                 (uint32_t)hdrs_cap, enc_blk_off, enc_blk, enc_flags, plan ? nencs : 0u, tabs, tab_ent, tab_ent_cap, reps,
+                                 item_off, item_len, item_policy, s->bp_hash.p, c->d_static)))
+        return rc;
+    if ((rc = slot_commit(c, s))) return rc;
+    return call_end(c, flags);
+}
+
+// The block encoder's device-plan path (hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE; not in the C ABI): the caller has
+// checked the inputs, so a void encoder here is a failure. One upload of the arena below the prefix area and of the
+// records; the two plan kernels; the ordered pack of the 3 nh items into a contiguous blob;
+// hpk_encode_strings_packed's steps with the item policies; the offsets at the block boundaries; then the tables,
+// their entries and the boundaries come back (the one wait before the end), and with the total known, exactly the bytes.
+int hpk_plan_device(hpk_ctx* c, hpk_planjob* job) {
+    job->bytes = nullptr;
+    job->us_up = job->us_plan = job->us_items = job->us_strings = job->us_back = 0;
+    const uint32_t nh = job->nh, ni = 3u * nh, nb = job->nblocks, ne = job->nencs;
+    const uint64_t arena_cap = (uint64_t)job->prefix_base + 4ull * nh;
+    const uint64_t in_cap = (uint64_t)job->field_off[2 * (size_t)nh] + 4ull * nh, out_cap = in_cap + 6ull * ni;
+    if (!nh || !nb || !ne || nh >= 0x20000000u || arena_cap > HPK_MAX_OFFSET || out_cap > HPK_MAX_OFFSET)
+        return hpk_set_err_msg("the block plan's arena or items pass the u32 offset range", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    static const bool timing = getenv("HPK_HENC_TIMING") != nullptr;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto lap = [&](std::chrono::steady_clock::time_point* t, long* us) {
+        if (timing) (void)hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        *us = (long)std::chrono::duration_cast<std::chrono::microseconds>(t1 - *t).count();
+        *t = t1;
+    };
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t at_foff = up16(arena_cap + 16), at_hoff = at_foff + up16(4 * (2 * (size_t)nh + 1));
+    const size_t at_eoff = at_hoff + up16(4 * ((size_t)nb + 1)), at_eblk = at_eoff + up16(4 * ((size_t)ne + 1));
+    const size_t at_flag = at_eblk + up16(4 * (size_t)nb), at_tabs = at_flag + up16(ne);
+    const size_t at_ent = at_tabs + up16(32 * (size_t)ne), at_reps = at_ent + up16(16 * (size_t)job->nent);
+    const size_t at_ioff = at_reps + 16 * (size_t)nh, at_ilen = at_ioff + up16(4 * (size_t)ni), at_ipol = at_ilen + up16(4 * (size_t)ni);
+    const size_t at_in = at_ipol + up16(ni), at_inoff = at_in + up16(in_cap + 16);
+    const size_t at_ooff = at_inoff + up16(4 * ((size_t)ni + 1)), at_olen = at_ooff + up16(4 * ((size_t)ni + 1));
+    const size_t at_st = at_olen + up16(4 * (size_t)ni), at_boff = at_st + up16(ni), at_out = at_boff + up16(4 * ((size_t)nb + 1));
+    const size_t tmp = hpk_pack_tmp_bytes(ni);
+    hpk_slot* s;
+    int rc;
+    if ((rc = apply_static(c)) || (rc = slot_acquire(c, &s)) ||
+        (rc = slot_reserve(c, s, {{&s->bp_hash, 8 * (size_t)nh + 8}, {&s->pk_tmp, tmp + 32}, {&s->bp_buf, at_out + out_cap + 16}})))
+        return rc;
+    auto t0 = now();
+    uint8_t* d = s->bp_buf.as<uint8_t>();
+    auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(d + at); };
+    auto up = [&](size_t at, const void* src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    };
+    HIP_TRY(up(0, job->arena, job->prefix_base));
+    HIP_TRY(up(at_foff, job->field_off, 4 * (2 * (size_t)nh + 1)));
+    HIP_TRY(up(at_hoff, job->hdr_off, 4 * ((size_t)nb + 1)));
+    HIP_TRY(up(at_eoff, job->enc_blk_off, 4 * ((size_t)ne + 1)));
+    HIP_TRY(up(at_eblk, job->enc_blk, 4 * (size_t)job->enc_blk_off[ne]));
+    HIP_TRY(up(at_flag, job->enc_flags, ne));
+    HIP_TRY(up(at_tabs, job->tabs, 32 * (size_t)ne));
+    HIP_TRY(up(at_ent, job->tab_ent, 16 * (size_t)job->nent));
+    lap(&t0, &job->us_up);
+    hpk_dtab* d_tabs = reinterpret_cast<hpk_dtab*>(d + at_tabs);
+    hpk_header* d_ent = reinterpret_cast<hpk_header*>(d + at_ent);
+    if ((rc = hpk_launch_blkplan(c, d, (uint32_t)arena_cap, 0u, job->fields_base, job->prefix_base, u32p(at_foff), u32p(at_hoff), nb, nh,
+                                 u32p(at_eoff), u32p(at_eblk), d + at_flag, ne, d_tabs, d_ent, job->nent,
+                                 reinterpret_cast<hpk_hrep*>(d + at_reps), u32p(at_ioff), u32p(at_ilen), d + at_ipol, s->bp_hash.p,
+                                 c->d_static)))
+        return rc;
+    lap(&t0, &job->us_plan);
+    if ((rc = hpk_pack_launch(c, d, (uint32_t)arena_cap, u32p(at_ioff), u32p(at_ilen), ni, d + at_in, (uint32_t)in_cap, u32p(at_inoff),
+                              s->pk_tmp.p, in_cap)))
+        return rc;
+    lap(&t0, &job->us_items);
+    if ((rc = strings_steps(c, s, tmp, d + at_in, (uint32_t)in_cap, u32p(at_inoff), ni, d + at_ipol, d + at_out, (uint32_t)out_cap,
+                            u32p(at_ooff), u32p(at_olen), d + at_st)) ||
+        (rc = hpk_launch_blkplan_boff(c, u32p(at_ooff), u32p(at_hoff), nb, u32p(at_boff))))
+        return rc;
+    lap(&t0, &job->us_strings);
+    HIP_TRY(hipMemcpyAsync(job->tabs, d_tabs, 32 * (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+    if (job->nent) HIP_TRY(hipMemcpyAsync(job->tab_ent, d_ent, 16 * (size_t)job->nent, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(job->block_off, d + at_boff, 4 * ((size_t)nb + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t total = job->block_off[nb];
+    uint8_t* bytes = static_cast<uint8_t*>(malloc(total ? total : 1));
+    if (!bytes) return hpk_set_err_msg("out of memory", HPK_E_INVAL);
+    hipError_t e = total > out_cap ? hipErrorInvalidValue : hipSuccess;
+    if (e == hipSuccess && total) e = hipMemcpyAsync(bytes, d + at_out, total, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        free(bytes);
+        return hpk_set_err("the planned blocks' bytes", e);
+    }
+    if ((rc = slot_commit(c, s)) || (rc = take_err(c))) {
+        free(bytes);
+        return rc;
+    }
+    lap(&t0, &job->us_back);
+    job->bytes = bytes;
     return HPK_E_OK;
 }
 

@@ -67,6 +67,10 @@ struct hpk_slot {
     DevBuf bs_meta, bs_stage, bs_out;
     // the block decoder's device-apply path: the lists, the tables, the results and the header records
     DevBuf ba_buf;
+    // the header-block plan (hpk_plan_blocks): the two hashes per header
+    DevBuf bp_hash;
+    // the block encoder's device-plan path: the arena, the lists, the tables, the items and the coded bytes
+    DevBuf bp_buf;
 };
 
 struct hpk_ctx {
@@ -75,6 +79,8 @@ struct hpk_ctx {
     int decode_kernel = HPK_DECODE_AUTO;  // hpk_ctx_set_decode_kernel
     int block_scan = HPK_BLOCK_SCAN_HOST;  // hpk_ctx_set_block_scan
     int block_apply = HPK_BLOCK_APPLY_HOST;  // hpk_ctx_set_block_apply
+    int block_plan = HPK_BLOCK_PLAN_HOST;  // hpk_ctx_set_block_plan
+    uint64_t plan_calls = 0;  // hpk_henc_encode_blocks calls the device-plan path answered (hpk_test_plan_calls)
     hpk_header* d_static = nullptr;  // hpk_static_table's 61 records, uploaded by the first hpk_apply_blocks
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
@@ -236,5 +242,18 @@ int hpk_launch_blkapply(hpk_ctx* c, const hpk_field* fields, const uint32_t* fie
                         const uint32_t* dec_blk_off, const uint32_t* dec_blk, uint32_t ndecs, hpk_dtab* tabs, hpk_header* tab_ent,
                         uint64_t tab_ent_cap, hpk_header* headers, uint32_t headers_cap, hpk_block_result* results,
                         const hpk_header* d_static);
+
+// The header-block plan's two kernels (hpk_blkplan.hip), on the ctx stream: hpk_plan_blocks' arguments as they are
+// (the capacities clamped to 32 bits), hashes 8 bytes of device scratch per header, and the static records in device
+// memory. The default-and-hash pass runs when hdrs_cap > 0, the plan kernel when there are encoders and blocks. reps
+// and tab_ent are 16-byte aligned, arena + prefix_base 4-byte aligned.
+int hpk_launch_blkplan(hpk_ctx* c, uint8_t* arena, uint32_t arena_cap, uint32_t static_base, uint32_t fields_base,
+                       uint32_t prefix_base, const uint32_t* field_off, const uint32_t* hdr_off, uint32_t nblocks, uint32_t hdrs_cap,
+                       const uint32_t* enc_blk_off, const uint32_t* enc_blk, const uint8_t* enc_flags, uint32_t nencs, hpk_dtab* tabs,
+                       hpk_header* tab_ent, uint64_t tab_ent_cap, hpk_hrep* reps, uint32_t* item_off, uint32_t* item_len,
+                       uint8_t* item_policy, void* hashes, const hpk_header* d_static);
+
+// boff[b] = out_off[3 * hdr_off[b]] for b <= nblocks: where block b's bytes begin in the strings call's output.
+int hpk_launch_blkplan_boff(hpk_ctx* c, const uint32_t* out_off, const uint32_t* hdr_off, uint32_t nblocks, uint32_t* boff);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

@@ -1322,6 +1322,14 @@ extern "C" int hpk_henc_set_max_table_size(hpk_henc* e, size_t n) {
     return HPK_E_OK;
 }
 
+extern "C" int hpk_henc_table_size(const hpk_henc* e, size_t* size, size_t* entries, size_t* max_size) {
+    if (!e) return HPK_E_INVAL;
+    if (size) *size = e->size;
+    if (entries) *entries = e->table.size();
+    if (max_size) *max_size = e->max_size;
+    return HPK_E_OK;
+}
+
 extern "C" int hpk_henc_encode(hpk_henc* e, const uint8_t* fields, const uint32_t* field_off, size_t n, uint8_t* out,
                                size_t cap, size_t* out_len) {
     if (!e || !out_len || (n && !field_off) || (cap && !out)) return HPK_E_INVAL;
@@ -1369,6 +1377,135 @@ extern "C" int hpk_henc_encode(hpk_henc* e, const uint8_t* fields, const uint32_
 static thread_local int t_fail_batches = 0;
 extern "C" void hpk_test_fail_batches(int n) { t_fail_batches = n > 0 ? n : 0; }
 
+// hpk_henc_encode_blocks with HPK_BLOCK_PLAN_DEVICE (include/hpk.h has the steps); the arguments are checked. Returns
+// HPK_E_OK with `out` filled and every encoder's table rebuilt, a negative error with every encoder as it was, or 1:
+// the host path is to answer the call (nothing has been touched).
+static int encode_blocks_planned(hpk_ctx* ctx, hpk_henc* const* encs, const uint8_t* fields, const uint32_t* field_off,
+                                 const uint32_t* hdr_off, uint32_t nblocks, hpk_henc_out* out) {
+    const uint32_t h0 = hdr_off[0], nh = hdr_off[nblocks] - h0;
+    if (!nh) return 1;
+    uint32_t ring = 0, chunk = 0, wge = 0, grp = 0;
+    (void)hpk_test_blkplan_geometry(&ring, &chunk, &wge, &grp);
+    // the blocks grouped by encoder: a counting pass, no encoder is copied
+    std::unordered_map<hpk_henc*, uint32_t> slot;
+    std::vector<hpk_henc*> who;
+    std::vector<uint32_t> of(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        auto it = slot.find(encs[b]);
+        if (it == slot.end()) {
+            it = slot.emplace(encs[b], (uint32_t)who.size()).first;
+            who.push_back(encs[b]);
+        }
+        of[b] = it->second;
+    }
+    const uint32_t ne = (uint32_t)who.size();
+    std::vector<uint32_t> eoff(ne + 1, 0), eblk(nblocks), lhdr(nblocks + 1);
+    for (uint32_t b = 0; b < nblocks; ++b) eoff[of[b] + 1] += 1;
+    for (uint32_t e = 0; e < ne; ++e) eoff[e + 1] += eoff[e];
+    {
+        std::vector<uint32_t> at(eoff.begin(), eoff.end() - 1);
+        for (uint32_t b = 0; b < nblocks; ++b) eblk[at[of[b]]++] = b;
+    }
+    for (uint32_t b = 0; b <= nblocks; ++b) lhdr[b] = hdr_off[b] - h0;
+    // the tables: deferral is the host's to see; an encoder gets the records its max_size can ever fill
+    const uint8_t* stext = nullptr;
+    size_t slen = 0;
+    (void)hpk_static_table(&stext, &slen, nullptr);
+    std::vector<hpk_dtab> tabs(ne);
+    std::vector<uint8_t> flags(ne);
+    uint64_t nent = 0, prior = 0;
+    for (uint32_t e = 0; e < ne; ++e) {
+        const hpk_henc& h = *who[e];
+        if (h.max_size > 32ull * ring || h.table.size() > ring) return 1;
+        const uint32_t need = (uint32_t)((h.max_size + 31) / 32), cnt = (uint32_t)h.table.size();
+        const uint32_t cap = std::min(ring, std::max(need, cnt));
+        tabs[e] = hpk_dtab{(uint32_t)nent, cap, cnt, (uint32_t)h.size, (uint32_t)h.max_size, HPK_DTAB_NO_LIMIT, 0u, 0u};
+        flags[e] = (uint8_t)(h.huffman ? 1 : 0);
+        nent += cap;
+        prior += h.size - 32ull * cnt;
+    }
+    const uint32_t f_lo = field_off[2 * (size_t)h0];
+    const uint64_t fbytes = field_off[2 * (size_t)hdr_off[nblocks]] - f_lo;
+    const uint64_t fields_base = slen + prior, prefix_base = (fields_base + fbytes + 3) & ~3ull;
+    if (prefix_base + 4ull * nh > HPK_MAX_OFFSET || fbytes + 4ull * nh + 18ull * nh > HPK_MAX_OFFSET || nent > 0x7FFFFFFFu ||
+        nh >= 0x20000000u)
+        return 1;
+    // the arena: the static text, every encoder's live entries' bytes, the fields
+    std::vector<uint8_t> arena(prefix_base);
+    std::vector<hpk_header> ent(nent ? nent : 1);
+    memcpy(arena.data(), stext, slen);
+    size_t at = slen;
+    for (uint32_t e = 0; e < ne; ++e) {
+        hpk_header* rec = ent.data() + tabs[e].ent;
+        for (const auto& kv : who[e]->table) {
+            *rec++ = hpk_header{(uint32_t)at, (uint32_t)kv.first.size(), (uint32_t)(at + kv.first.size()), (uint32_t)kv.second.size()};
+            memcpy(arena.data() + at, kv.first.data(), kv.first.size());
+            memcpy(arena.data() + at + kv.first.size(), kv.second.data(), kv.second.size());
+            at += kv.first.size() + kv.second.size();
+        }
+    }
+    if (fbytes) memcpy(arena.data() + fields_base, fields + f_lo, fbytes);
+    std::vector<uint32_t> lfo(2 * (size_t)nh + 1);
+    for (size_t k = 0; k <= 2 * (size_t)nh; ++k) lfo[k] = field_off[2 * (size_t)h0 + k] - f_lo;
+    if (t_fail_batches > 0) {
+        --t_fail_batches;
+        return hpk_set_err_msg("injected batch failure (hpk_test_fail_batches)", HPK_E_DEVICE);
+    }
+    out->block_off = (uint32_t*)malloc((nblocks + 1) * sizeof(uint32_t));
+    if (!out->block_off) return HPK_E_INVAL;
+    hpk_planjob job{};
+    job.arena = arena.data();
+    job.fields_base = (uint32_t)fields_base;
+    job.prefix_base = (uint32_t)prefix_base;
+    job.field_off = lfo.data();
+    job.hdr_off = lhdr.data();
+    job.nblocks = nblocks;
+    job.nh = nh;
+    job.enc_blk_off = eoff.data();
+    job.enc_blk = eblk.data();
+    job.enc_flags = flags.data();
+    job.nencs = ne;
+    job.tabs = tabs.data();
+    job.tab_ent = ent.data();
+    job.nent = (uint32_t)nent;
+    job.block_off = out->block_off;
+    int rc = hpk_plan_device(ctx, &job);
+    if (getenv("HPK_HENC_TIMING"))
+        fprintf(stderr, "hpk_henc plan path: up %ld us, plan %ld us, items %ld us, strings %ld us, back %ld us\n", job.us_up, job.us_plan,
+                job.us_items, job.us_strings, job.us_back);
+    bool whole = true;
+    for (uint32_t e = 0; e < ne && !rc; ++e) whole &= tabs[e].applied == eoff[e + 1] - eoff[e];
+    if (rc || !whole) {
+        free(job.bytes);
+        hpk_henc_out_free(out);
+        return rc ? rc : 1;
+    }
+    // every table rebuilt from its final entries' bytes, all of which lie in the host's arena; then the commit
+    std::vector<std::deque<std::pair<std::string, std::string>>> fresh(ne);
+    for (uint32_t e = 0; e < ne; ++e) {
+        const hpk_header* rec = ent.data() + tabs[e].ent;
+        for (uint32_t i = 0; i < tabs[e].count; ++i) {
+            const hpk_header& r = rec[i];
+            if ((uint64_t)r.name_off + r.name_len > arena.size() || (uint64_t)r.value_off + r.value_len > arena.size()) {
+                free(job.bytes);
+                hpk_henc_out_free(out);
+                return hpk_set_err_msg("the block plan returned an entry outside the arena", HPK_E_DEVICE);
+            }
+            fresh[e].emplace_back(std::string((const char*)arena.data() + r.name_off, r.name_len),
+                                  std::string((const char*)arena.data() + r.value_off, r.value_len));
+        }
+    }
+    for (uint32_t e = 0; e < ne; ++e) {
+        who[e]->table = std::move(fresh[e]);
+        who[e]->size = tabs[e].size;
+    }
+    hpk_ctx_plan_answered(ctx);
+    out->bytes = job.bytes;
+    out->len = out->block_off[nblocks];
+    out->n_blocks = nblocks;
+    return HPK_E_OK;
+}
+
 extern "C" int hpk_henc_encode_blocks(hpk_ctx* ctx, hpk_henc* const* encs, const uint8_t* fields,
                                       const uint32_t* field_off, const uint32_t* hdr_off, uint32_t nblocks,
                                       hpk_henc_out* out) {
@@ -1381,6 +1518,10 @@ extern "C" int hpk_henc_encode_blocks(hpk_ctx* ctx, hpk_henc* const* encs, const
     for (uint32_t k = 2 * hdr_off[0]; k < 2 * hdr_off[nblocks]; ++k)
         if (field_off[k + 1] < field_off[k]) return HPK_E_INVAL;
     if (nh && field_off[2 * hdr_off[nblocks]] > field_off[2 * hdr_off[0]] && !fields) return HPK_E_INVAL;
+    if (ctx && hpk_ctx_block_plan(ctx) == HPK_BLOCK_PLAN_DEVICE) {  // opt-in: the table logic on the device too
+        const int rc = encode_blocks_planned(ctx, encs, fields, field_off, hdr_off, nblocks, out);
+        if (rc <= 0) return rc;
+    }
     // Pass 1 runs against a working copy of each distinct encoder (hpk_henc_encode's `next = *e`);
     // the copies replace the encoders only once every block is assembled, so a call that fails in
     // the Huffman batch or the assembly leaves each dynamic table as it was and the peer's decoder

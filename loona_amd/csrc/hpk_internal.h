@@ -50,5 +50,34 @@ struct hpk_applyplan {
 };
 int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o,
                       hpk_applyplan* plan = nullptr);
+
+// The block encoder's device-plan path (hpk_ctx.hip: hpk_plan_device; used by hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE):
+// the host lays out hpk_plan_blocks' inputs, the device plans, gathers the items with the ordered pack and codes them
+// with hpk_encode_strings_packed's steps. Everything is on the host when it returns HPK_E_OK.
+struct hpk_planjob {
+    // in (host memory): hpk_plan_blocks' arguments; the static text lies at 0 of the arena, of which the bytes below
+    // prefix_base go up and the 4 * nh bytes of the prefix area are only reserved; hdr_off starts at 0
+    const uint8_t* arena;
+    uint32_t fields_base, prefix_base;
+    const uint32_t* field_off;  // 2 nh + 1
+    const uint32_t* hdr_off;    // nblocks + 1
+    uint32_t nblocks, nh;
+    const uint32_t* enc_blk_off;
+    const uint32_t* enc_blk;
+    const uint8_t* enc_flags;
+    uint32_t nencs;
+    // in / out (host memory): the tables, and their final entries
+    hpk_dtab* tabs;
+    hpk_header* tab_ent;
+    uint32_t nent;
+    // out: block b's bytes are bytes[block_off[b] .. block_off[b+1]); block_off the caller's (nblocks + 1), bytes
+    // from malloc, the caller's to free (null when the call fails)
+    uint32_t* block_off;
+    uint8_t* bytes;
+    long us_up, us_plan, us_items, us_strings, us_back;  // wall times of the passes (the stream is waited for only under HPK_HENC_TIMING)
+};
+int hpk_plan_device(hpk_ctx* c, hpk_planjob* job);
+void hpk_ctx_plan_answered(hpk_ctx* c);    // the caller has committed such a call's tables (hpk_test_plan_calls counts it)
+int hpk_ctx_block_plan(const hpk_ctx* c);  // hpk_ctx_set_block_plan's value (HPK_BLOCK_PLAN_HOST for no context)
 int hpk_ctx_block_scan(const hpk_ctx* c);  // hpk_ctx_set_block_scan's value (HPK_BLOCK_SCAN_HOST for no context)
 int hpk_ctx_block_apply(const hpk_ctx* c);  // hpk_ctx_set_block_apply's value (HPK_BLOCK_APPLY_HOST for no context)

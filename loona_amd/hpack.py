@@ -179,6 +179,12 @@ class Encoder:
     def set_max_table_size(self, n: int):
         _lib.check(self._L.hpk_henc_set_max_table_size(self._h, n), "hpk_henc_set_max_table_size")
 
+    def table_size(self):
+        """(size in octets per RFC 7541 §4.1, entries, max size), as Decoder.table_size."""
+        a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(self._L.hpk_henc_table_size(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "hpk_henc_table_size")
+        return a.value, b.value, c.value
+
     def encode(self, headers) -> bytes:
         """encoder.rs:210-217: the header block for [(name, value)] (bytes)."""
         parts, off = [], [0]
