@@ -1,6 +1,6 @@
 // hpk_blkscan.hip — the header-block scan's own kernels (hpk_scan_blocks): the table-free half of
 // Decoder::decode_with_cb (crates/loona-hpack/src/decoder.rs:368-450) on many blocks at once. A translation unit
-// of its own. The call's steps (hpk_ctx.hip strings them together):
+// of its own. The call's steps (hpk_calls_blocks.hip strings them together):
 //   * hpk_blkcount below, one lane per block (per-lane code in hpk_blkscan.h): the block's field count, its
 //     listed-string count and its status (HPK_OK, or HPK_BAD_OFFSETS with the sticky flag and both counts 0);
 //   * hpk_len_scan (hpk_pack.hip, as it is) over each count array: field_off and str_blk_off;

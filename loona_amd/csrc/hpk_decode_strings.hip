@@ -1,7 +1,7 @@
 // hpk_decode_strings.hip — the packed string-literal decode's own kernels (hpk_decode_strings_packed): RFC 7541
 // §5.2 string literals as decode_string reads them (crates/loona-hpack/src/decoder.rs:135-163), each in a window
 // of the input blob, raw and Huffman mixed, coming back end to end. A translation unit of its own: the decode
-// kernels and the ordered pack stay alone in their modules. The call's steps (hpk_ctx.hip strings them together):
+// kernels and the ordered pack stay alone in their modules. The call's steps (hpk_calls_strings.hip strings them together):
 //   * hpk_strparse below, one thread per string (per-thread code in hpk_strparse.h): the length integer, the
 //     length check and the H bit give a parse status, the payload's start, `consumed`, and two lengths of which
 //     at most one is nonzero: hlen (a Huffman payload's bytes) and rlen (a raw payload's);

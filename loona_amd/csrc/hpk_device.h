@@ -32,8 +32,8 @@ struct DevBuf {
 // The scratch of the device-pointer calls on one stream. Calls on different streams may overlap, so each
 // stream that uses the context gets a slot of its own (two calls on two streams never share a list, a
 // layout or the cursor: ADVICE r4); a stream's calls are ordered, so its slot is reused without a wait.
-// A call takes its stream's slot (slot_acquire), sizes the buffers it uses (slot_reserve), launches, and
-// marks the slot used after its last operation on the stream (slot_commit), all in hpk_ctx.hip. The rules:
+// A call takes its stream's slot (hpk_slot_acquire), sizes the buffers it uses (hpk_slot_reserve), launches, and
+// marks the slot used after its last operation on the stream (hpk_slot_commit), all in hpk_ctx.hip. The rules:
 //   * While only the context's own stream has used it, no event is created or recorded (an event record
 //     per launch cost about 1 us of a ~23 us small call).
 //   * The first use by a second stream switches to events. It synchronises the own stream once, and clears
@@ -71,7 +71,17 @@ struct hpk_slot {
     DevBuf bp_hash;
     // the block encoder's device-plan path: the arena, the lists, the tables, the items and the coded bytes
     DevBuf bp_buf;
+    // every buffer above: the one list of them (hpk_ctx_destroy frees through it)
+    static constexpr size_t kBufs = 17;
+    template <class F>
+    void each_buf(F f) {
+        for (DevBuf* b : {&long_list, &cp_bound, &cp_tmp, &cp_cursor, &pk_scratch, &pk_bound, &pk_tmp, &str_stage, &sd_meta, &sd_hblob,
+                          &sd_stage, &bs_meta, &bs_stage, &bs_out, &ba_buf, &bp_hash, &bp_buf})
+            f(*b);
+    }
 };
+// (the buffers are the slot's last members: one added and not listed in each_buf fails here)
+static_assert(sizeof(hpk_slot) == offsetof(hpk_slot, long_list) + hpk_slot::kBufs * sizeof(DevBuf), "hpk_slot::each_buf");
 
 struct hpk_ctx {
     int device = 0;

@@ -30,18 +30,9 @@
 #include <vector>
 
 #include "../../include/hpk.h"
-#include "hpk_internal.h"  // hpk_blocks_device: the device-scan path
+#include "hpk_internal.h"  // the context's calls that are not in the C ABI: the chunked host batch, the device paths
 
 int hpk_set_err_msg(const char* what, int code);  // hpk_ctx.hip: hpk_last_error's message
-// hpk_ctx.hip: the context's page-locked host staging area, grown to at least `bytes` (grow-only)
-int hpk_ctx_pinned(hpk_ctx* ctx, size_t bytes, void** p);
-// hpk_ctx.hip: a trusted host batch whose chunks can be waited for one by one (not in the C ABI)
-int hpk_decode_host_begin(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
-                          uint8_t* out_blob, size_t out_cap, const uint32_t* out_off, uint32_t* out_len,
-                          uint8_t* status, int* nchunks, uint32_t* cut);
-int hpk_host_chunk_wait(hpk_ctx* c, int j);
-int hpk_decode_host_end(hpk_ctx* c);
-int hpk_ctx_max_chunks();
 
 namespace {
 

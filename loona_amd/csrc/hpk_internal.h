@@ -1,5 +1,5 @@
-// hpk_internal.h — declarations shared between the host (hpk_cpu.cpp) and device (hpk_gpu.hip)
-// halves of libhpk. Not part of the C ABI.
+// hpk_internal.h — declarations shared between the host units of libhpk (hpk_cpu.cpp, hpk_hpack.cpp) and its
+// device half (hpk_ctx.hip and the hpk_calls_*.hip call layer). Not part of the C ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -13,7 +13,17 @@ int hpk_cpu_decode(const hpk_tables* t, const uint8_t* in, size_t n, uint8_t* ou
 int hpk_cpu_encode(const hpk_tables* t, const uint8_t* in, size_t n, uint8_t* out, size_t cap,
                    size_t* out_len);
 
-// The block decoder's device-scan path (hpk_ctx.hip: hpk_blocks_device; used by hpk_hpack.cpp): what it leaves
+// hpk_ctx.hip: the context's page-locked host staging area, grown to at least `bytes` (grow-only)
+int hpk_ctx_pinned(hpk_ctx* ctx, size_t bytes, void** p);
+// hpk_calls_batch.hip: a trusted host batch whose chunks can be waited for one by one (the block decoder's form)
+int hpk_decode_host_begin(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,
+                          uint8_t* out_blob, size_t out_cap, const uint32_t* out_off, uint32_t* out_len,
+                          uint8_t* status, int* nchunks, uint32_t* cut);
+int hpk_host_chunk_wait(hpk_ctx* c, int j);
+int hpk_decode_host_end(hpk_ctx* c);
+int hpk_ctx_max_chunks();
+
+// The block decoder's device-scan path (hpk_calls_blocks.hip: hpk_blocks_device; used by hpk_hpack.cpp): what it leaves
 // in the context's page-locked area, valid until the context's next block call.
 struct hpk_blkdev {
     const hpk_field* fields;
@@ -51,7 +61,7 @@ struct hpk_applyplan {
 int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o,
                       hpk_applyplan* plan = nullptr);
 
-// The block encoder's device-plan path (hpk_ctx.hip: hpk_plan_device; used by hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE):
+// The block encoder's device-plan path (hpk_calls_blocks.hip: hpk_plan_device; used by hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE):
 // the host lays out hpk_plan_blocks' inputs, the device plans, gathers the items with the ordered pack and codes them
 // with hpk_encode_strings_packed's steps. Everything is on the host when it returns HPK_E_OK.
 struct hpk_planjob {
