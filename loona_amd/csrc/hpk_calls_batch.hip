@@ -66,21 +66,7 @@ static int host_begin(launch_fn fn, hpk_ctx* c, const uint8_t* in_blob, size_t i
             HIP_TRY(hipEventCreateWithFlags(&c->ev_out[j], hipEventDisableTiming));
         }
     }
-    const size_t kChunkBytes = (size_t)4 << 20;
-    int chunks = (int)((in_bytes + out_bytes) / kChunkBytes);
-    chunks = chunks < 1 ? 1 : (chunks > hpk_ctx::kMaxChunks ? hpk_ctx::kMaxChunks : chunks);
-    if ((uint32_t)chunks > n) chunks = (int)n;
-    cut[0] = 0;
-    for (int j = 1; j < chunks; ++j) {  // first literal whose end passes j/chunks of the bytes
-        const uint64_t target = (uint64_t)in_bytes * j / chunks;
-        uint32_t lo = cut[j - 1], hi = n;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (in_off[mid + 1] < target) lo = mid + 1; else hi = mid;
-        }
-        cut[j] = lo;
-    }
-    cut[chunks] = n;
+    const int chunks = hpk_chunk_cuts(in_off, n, out_bytes, cut);  // (hpk_chunks.h)
     // A failure after some chunk's copies were queued leaves DMA into and out of the caller's buffers
     // (and the pinned staging area the block decoder reuses) in flight: drain the three streams before
     // returning, so nothing lands after the call has returned.

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/hpk.h"
+#include "hpk_chunks.h"
 #include "hpk_code.h"
 #include "hpk_internal.h"
 
@@ -112,7 +113,7 @@ struct hpk_ctx {
     void* h_pin = nullptr;
     size_t h_pin_cap = 0;
     // host-pointer pipeline: copy-in and copy-out streams + per-chunk events (created lazily)
-    static constexpr int kMaxChunks = 8;
+    static constexpr int kMaxChunks = kHpkMaxChunks;  // (hpk_chunks.h)
     hipStream_t h2d = nullptr;
     hipStream_t d2h = nullptr;
     hipEvent_t ev_in[kMaxChunks] = {};
