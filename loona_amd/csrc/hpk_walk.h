@@ -143,6 +143,20 @@ struct Lit12 {
 };
 
 // (Re)load the pair and the next dword at X.
+// Contract: reads win32[(X >> 5) - 1], the dword BEFORE the one holding X, as well as that one and the next. With
+// P = X - 31 the first bit wanted, that dword lies in front of the window exactly when P is the window's first bit
+// (a literal at byte 0 of a dword-aligned window): then X % 32 == 31, every use of d0 is alignbit(d0, d1, ~X) with a
+// shift of ~X & 31 == 0, which returns d1, and the first step that advances crosses a dword and replaces d0 by d1. So
+// its value never reaches a result, but the callers keep it addressable (win_at reads the same dword):
+//   hpk_wave.h          win32 is the LDS array's base and X carries the wave's offset (wbits): the dword is the last
+//                       one of the dummy area (kWaveOff = kDummyOff + 256) for wave 0, else of the previous wave's image;
+//   hpk_fill.h          win32 = smem + kInOff: the last dword of the two-symbol table (kInOff = kTabBytes + kLutBytes);
+//   hpk_persist_lit.h   a lane's input slot starts with a pad dword for this read (sb >= 32; never written, never used);
+//   hpk_long.h          its own copy of this load: ring[((j - 1) & (kRing - 1)) * kBlock] wraps inside the lane's ring;
+//   hpk_huge_piece.h    does not load pairs: HugeWalk only reads forward, 16-byte chunks clamped to the batch's last one.
+// The lane replays (tests/emu/emu.cpp, tail_emu.cpp, walk13_emu.cpp, tailword_emu.cpp) run every fill with that dword all
+// zeros and all ones and require the same lengths, statuses and image; under a host sanitizer it is the first dword of
+// the window's allocation.
 __device__ __forceinline__ void lit12_load(Lit12& L, const uint32_t* __restrict__ win32) {
     const uint32_t* p = win32 + (L.X >> 5);
     L.d0 = p[-1];

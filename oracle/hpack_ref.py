@@ -215,7 +215,14 @@ class Decoder:
         return (name, value), consumed + n
 
     def decode(self, buf: bytes):
+        """Decoder::decode (decoder.rs:455-469): the headers, or the first error."""
         out = []
+        self.decode_with_cb(buf, lambda n, v: out.append((n, v)))
+        return out
+
+    def decode_with_cb(self, buf: bytes, cb):
+        """Decoder::decode_with_cb (decoder.rs:368-450): cb(name, value) per header as it is decoded, so the headers
+        before the first error have been emitted when it is raised."""
         i = 0
         last_was_size_update = False
         while i < len(buf):
@@ -224,10 +231,10 @@ class Decoder:
             last_was_size_update = False
             if b & 128:
                 index, consumed = decode_integer(rest, 7)
-                out.append(self.get_from_table(index))
+                cb(*self.get_from_table(index))
             elif b & 64:
                 (n, v), consumed = self._decode_literal(rest, True)
-                out.append((n, v))
+                cb(n, v)
                 self.dynamic.add_header(n, v)
             elif b & 32:
                 last_was_size_update = True
@@ -237,11 +244,10 @@ class Decoder:
                 self.dynamic.set_max_table_size(new_size)
             else:  # 0001xxxx never indexed, 0000xxxx without indexing
                 (n, v), consumed = self._decode_literal(rest, False)
-                out.append((n, v))
+                cb(n, v)
             i += consumed
         if last_was_size_update:
             raise DecoderError("SizeUpdateAtEnd")
-        return out
 
 
 def encode_integer(value: int, prefix: int, leading: int = 0) -> bytes:

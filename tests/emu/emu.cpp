@@ -68,50 +68,71 @@ static int run_lanes(std::mt19937_64& rng, int nlit, int maxlen) {
             cap[t] = nb[t] * 8 / 5;
             op += cap[t];
         }
-        win.resize(win.size() + 64, 0x5A);
-        std::vector<uint32_t> w32(win.size() / 4 + 4, 0);
-        for (size_t j = 0; j + 4 <= win.size(); j += 4)
-            w32[j / 4] = ((uint32_t)win[j] << 24) | ((uint32_t)win[j + 1] << 16) | ((uint32_t)win[j + 2] << 8) | win[j + 3];
-        std::vector<uint8_t> img(op + 256 + 64, 0xEE);
+        // The window as the walk may read it, and not a dword more (so a host sanitizer sees the true edges): one
+        // guard dword in front (lit12_load reads the dword before the one holding X: w32[-1] for a literal at byte 0
+        // of the window, which `mis == 0` places there), the literals, and the two dwords a step reads ahead of the
+        // one holding X ((X >> 5) + 1 and + 2, X <= Eb). Bytes past the last literal are 0x5A.
+        const size_t nd = (win.size() * 8 + 31) / 32 + 3;
+        win.resize(nd * 4, 0x5A);
+        std::vector<uint32_t> store(1 + nd, 0);
+        uint32_t* const w32 = store.data() + 1;
+        for (size_t j = 0; j < nd; ++j)
+            w32[j] = ((uint32_t)win[4 * j] << 24) | ((uint32_t)win[4 * j + 1] << 16) | ((uint32_t)win[4 * j + 2] << 8) | win[4 * j + 3];
         const uint32_t dmy = op + 64 + 4;  // the lane's dummy dword, past the regions
-        std::vector<uint32_t> olen(k), ost(k);
         const uint32_t* lut = kTab == 3 ? T.lut3 : T.lut2;
-        for (int lane = 63; lane >= 0; --lane) {
-            const uint32_t t1 = lane, t2 = 127 - lane;
-            auto load = [&](Lit12& Z, uint32_t tt) {
-                const uint32_t u = std::min<uint32_t>(tt, k - 1);
-                Z.act = tt < k;
-                Z.idx = tt;
-                Z.X = p0[u] * 8u + 31u;
-                Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
-                Z.o = o0[u];
-                Z.o0 = o0[u];
-                Z.st = HPK_OK;
-                Z.prog = false;
-                lit12_load(Z, w32.data());
-            };
-            Lit12 L, N;
-            load(L, t1);
-            load(N, t2);
-            bool body = L.Eb - L.X >= kBodyMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            Lit12 A = L;
-            L = N;
-            body = L.Eb - L.X >= kBodyMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            N = L;
-            L = A;  // restored as the kernels do: Eb from the queue entry, window reloaded at X
-            const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
-            L.Eb = L.st != HPK_OK ? L.X : p0[u1] * 8u + 31u + (L.act ? nb[u1] * 8u : 0u);
-            lit12_load(L, w32.data());
-            L.more = L.Eb - L.X >= 5u;
-            N.more = N.Eb - N.X >= 5u;
-            for (int guard = 0; (L.more || N.more) && guard < 1000000; ++guard) {
-                if (L.more) lit12_step<kPred, kWave, kTab, true>(L, w32.data(), lut, T.lo, img.data(), kWave ? dmy : dmy);
-                if (N.more) lit12_step<kPred, kWave, kTab, true>(N, w32.data(), lut, T.lo, img.data(), dmy);
+        // One fill with the guard dword set to `guard`: the lengths, the statuses and the image.
+        auto fill = [&](uint32_t guard, std::vector<uint32_t>& olen, std::vector<uint32_t>& ost, std::vector<uint8_t>& img) {
+            store[0] = guard;
+            olen.assign(k, 0);
+            ost.assign(k, 0);
+            img.assign(op + 256 + 64, 0xEE);
+            for (int lane = 63; lane >= 0; --lane) {
+                const uint32_t t1 = lane, t2 = 127 - lane;
+                auto load = [&](Lit12& Z, uint32_t tt) {
+                    const uint32_t u = std::min<uint32_t>(tt, k - 1);
+                    Z.act = tt < k;
+                    Z.idx = tt;
+                    Z.X = p0[u] * 8u + 31u;
+                    Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
+                    Z.o = o0[u];
+                    Z.o0 = o0[u];
+                    Z.st = HPK_OK;
+                    Z.prog = false;
+                    lit12_load(Z, w32);
+                };
+                Lit12 L, N;
+                load(L, t1);
+                load(N, t2);
+                bool body = L.Eb - L.X >= kBodyMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                Lit12 A = L;
+                L = N;
+                body = L.Eb - L.X >= kBodyMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                N = L;
+                L = A;  // restored as the kernels do: Eb from the queue entry, window reloaded at X
+                const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
+                L.Eb = L.st != HPK_OK ? L.X : p0[u1] * 8u + 31u + (L.act ? nb[u1] * 8u : 0u);
+                lit12_load(L, w32);
+                L.more = L.Eb - L.X >= 5u;
+                N.more = N.Eb - N.X >= 5u;
+                for (int guard_it = 0; (L.more || N.more) && guard_it < 1000000; ++guard_it) {
+                    if (L.more) lit12_step<kPred, kWave, kTab, true>(L, w32, lut, T.lo, img.data(), dmy);
+                    if (N.more) lit12_step<kPred, kWave, kTab, true>(N, w32, lut, T.lo, img.data(), dmy);
+                }
+                if (L.act) olen[t1] = L.o - L.o0, ost[t1] = lit12_status(L);
+                if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
             }
-            if (L.act) olen[t1] = L.o - L.o0, ost[t1] = lit12_status(L);
-            if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
+        };
+        // The guard dword's value must not reach a result (lit12_load's contract, hpk_walk.h): the fill run with it
+        // all zeros and all ones gives the same lengths, statuses and image, byte for byte.
+        std::vector<uint32_t> olen, ost, olen1, ost1;
+        std::vector<uint8_t> img, img1;
+        fill(0x00000000u, olen, ost, img);
+        fill(0xFFFFFFFFu, olen1, ost1, img1);
+        if (olen != olen1 || ost != ost1 || img != img1) {
+            if (bad < 5) printf("lanes tab %d wave %d: fill at %zu depends on the dword before its window\n", kTab, (int)kWave, f);
+            ++bad;
         }
         for (size_t t = 0; t < k; ++t) {
             std::vector<uint8_t> ref(cap[t] + 8);
@@ -149,10 +170,12 @@ static int replay_huge(const std::vector<uint8_t>& enc, uint32_t lanes, uint32_t
     const uint32_t* lut = kTab == 4 ? T.lut13 : kTab == 3 ? T.lut3 : T.lut2;
     int bad = 0;
     const uint32_t nb = enc.size();
-    std::vector<uint8_t> inb(16 + in_mis + nb + 64, 0x5A);
+    // the input ends with its last 16-byte chunk (ld16 clamps to it, as the kernels clamp to the batch's last chunk):
+    // a read past it is a host sanitizer's to report
+    const uint32_t last16 = (in_mis + nb - 1) >> 4;
+    std::vector<uint8_t> inb(16 + 16 * ((size_t)last16 + 1), 0x5A);
     memcpy(inb.data() + 16 + in_mis, enc.data(), nb);
     const uint8_t* in_base = inb.data() + 16;  // (16-byte aligned)
-    const uint32_t last16 = (in_mis + nb - 1) >> 4;
     auto ld16 = [&](uint32_t ci) {
         uint4 v;
         memcpy(&v, in_base + 16 * std::min(ci, last16), 16);

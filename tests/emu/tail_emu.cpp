@@ -204,7 +204,7 @@ static int run_lanes(std::mt19937_64& rng, int nlit, int maxlen, long* slow_lane
     int bad = 0;
     for (size_t f = 0; f < lits.size(); f += 128) {
         const size_t k = std::min<size_t>(128, lits.size() - f);
-        const uint32_t mis = 4 + rng() % 12;  // (>= 4: the walk reads the dword before a literal's first)
+        const uint32_t mis = rng() % 16;  // (0: a literal at byte 0 of the window, the guard dword in front of it)
         std::vector<uint8_t> win(mis);
         std::vector<uint32_t> p0(k), nb(k), o0(k), cap(k);
         const uint32_t ofirst = 4 + rng() % 4;
@@ -217,68 +217,90 @@ static int run_lanes(std::mt19937_64& rng, int nlit, int maxlen, long* slow_lane
             cap[t] = nb[t] * 8 / 5;
             op += cap[t];
         }
-        win.resize(win.size() + 64, 0x5A);
-        std::vector<uint32_t> w32(win.size() / 4 + 4, 0);
-        for (size_t j = 0; j + 4 <= win.size(); j += 4)
-            w32[j / 4] = ((uint32_t)win[j] << 24) | ((uint32_t)win[j + 1] << 16) | ((uint32_t)win[j + 2] << 8) | win[j + 3];
+        // The window as the walk may read it and not a dword more, so that a host sanitizer sees the true edges: one guard
+        // dword in front (lit12_load reads the dword before the one holding X: w32[-1] for a literal at byte 0 of the
+        // window, which mis == 0 places there), the literals, and the two dwords a step reads ahead of the one holding X
+        // ((X >> 5) + 1 and + 2, X <= Eb). Bytes past the last literal are 0x5A.
+        const size_t nd = (win.size() * 8 + 31) / 32 + 3;
+        win.resize(nd * 4, 0x5A);
+        std::vector<uint32_t> store(1 + nd, 0);
+        uint32_t* const w32 = store.data() + 1;
+        for (size_t j = 0; j < nd; ++j)
+            w32[j] = ((uint32_t)win[4 * j] << 24) | ((uint32_t)win[4 * j + 1] << 16) | ((uint32_t)win[4 * j + 2] << 8) | win[4 * j + 3];
         std::vector<uint8_t> img(op + 256 + 64, 0xEE);
         const uint32_t dmy = op + 64 + 4;  // the lane's dummy dword, past the regions
         std::vector<uint32_t> olen(k), ost(k);
         const uint32_t* lut = kTab == 3 ? T.lut3 : T.lut2;
-        for (int lane = 63; lane >= 0; --lane) {
-            const uint32_t t1 = lane, t2 = 127 - lane;
-            auto load = [&](Lit12& Z, uint32_t tt) {
-                const uint32_t u = std::min<uint32_t>(tt, k - 1);
-                Z.act = tt < k;
-                Z.idx = tt;
-                Z.X = p0[u] * 8u + 31u;
-                Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
-                Z.o = o0[u];
-                Z.o0 = o0[u];
-                Z.st = HPK_OK;
-                Z.prog = false;
-                lit12_load(Z, w32.data());
-            };
-            Lit12 L, N;
-            load(L, t1);
-            load(N, t2);
-            bool body = L.Eb - L.X >= kBodyMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            Lit12 A = L;
-            L = N;
-            body = L.Eb - L.X >= kBodyMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            N = L;
-            L = A;  // restored as the kernel does: Eb from the queue entry, window reloaded at X
-            const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
-            L.Eb = L.st != HPK_OK ? L.X : p0[u1] * 8u + 31u + (L.act ? nb[u1] * 8u : 0u);
-            lit12_load(L, w32.data());
-            L.more = L.Eb - L.X >= 5u;
-            N.more = N.Eb - N.X >= 5u;
-            {  // hpk_wave.h's tail block: the two chains' lookups in turn
-                Tail12 TL, TN;
-                tail12_begin(TL, L);
-                tail12_begin(TN, N);
-                for (int s = 0; s < 4; ++s) {
-                    tail12_look<kPred, kTab>(TL, lut, img.data(), dmy);
-                    tail12_look<kPred, kTab>(TN, lut, img.data(), dmy);
+        // The guard dword's value must not reach a result (lit12_load's contract, hpk_walk.h): the fill runs twice, with it
+        // all zeros and all ones, and must give the same lengths, statuses and image, byte for byte.
+        std::vector<uint32_t> olen0, ost0;
+        std::vector<uint8_t> img0;
+        for (int pass = 0; pass < 2; ++pass) {
+            store[0] = pass ? 0xFFFFFFFFu : 0x00000000u;
+            img.assign(img.size(), 0xEE);
+            olen.assign(k, 0);
+            ost.assign(k, 0);
+            for (int lane = 63; lane >= 0; --lane) {
+                const uint32_t t1 = lane, t2 = 127 - lane;
+                auto load = [&](Lit12& Z, uint32_t tt) {
+                    const uint32_t u = std::min<uint32_t>(tt, k - 1);
+                    Z.act = tt < k;
+                    Z.idx = tt;
+                    Z.X = p0[u] * 8u + 31u;
+                    Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
+                    Z.o = o0[u];
+                    Z.o0 = o0[u];
+                    Z.st = HPK_OK;
+                    Z.prog = false;
+                    lit12_load(Z, w32);
+                };
+                Lit12 L, N;
+                load(L, t1);
+                load(N, t2);
+                bool body = L.Eb - L.X >= kBodyMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                Lit12 A = L;
+                L = N;
+                body = L.Eb - L.X >= kBodyMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                N = L;
+                L = A;  // restored as the kernel does: Eb from the queue entry, window reloaded at X
+                const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
+                L.Eb = L.st != HPK_OK ? L.X : p0[u1] * 8u + 31u + (L.act ? nb[u1] * 8u : 0u);
+                lit12_load(L, w32);
+                L.more = L.Eb - L.X >= 5u;
+                N.more = N.Eb - N.X >= 5u;
+                {  // hpk_wave.h's tail block: the two chains' lookups in turn
+                    Tail12 TL, TN;
+                    tail12_begin(TL, L);
+                    tail12_begin(TN, N);
+                    for (int s = 0; s < 4; ++s) {
+                        tail12_look<kPred, kTab>(TL, lut, img.data(), dmy);
+                        tail12_look<kPred, kTab>(TN, lut, img.data(), dmy);
+                    }
+                    L.more &= tail12_end(TL, L);
+                    N.more &= tail12_end(TN, N);
+                    if (pass == 0) *slow_lanes += (int)L.more + (int)N.more;
                 }
-                L.more &= tail12_end(TL, L);
-                N.more &= tail12_end(TN, N);
-                *slow_lanes += (int)L.more + (int)N.more;
+                for (int guard = 0; (L.more || N.more) && guard < 1000000; ++guard) {
+                    if (L.more) lit12_step<kPred, true, kTab, true>(L, w32, lut, T.lo, img.data(), dmy);
+                    if (N.more) lit12_step<kPred, true, kTab, true>(N, w32, lut, T.lo, img.data(), dmy);
+                }
+                // results as the kernel's: the first slot's status from its end position and the window
+                // (its dword pair is not kept), the second's from the walk
+                if (L.act) {
+                    const uint32_t Eb = p0[u1] * 8u + 31u + nb[u1] * 8u;
+                    olen[t1] = L.o - L.o0;
+                    ost[t1] = L.st != HPK_OK ? L.st : residual_status(Eb - L.X, win_at(w32, L.X - 31u));
+                }
+                if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
             }
-            for (int guard = 0; (L.more || N.more) && guard < 1000000; ++guard) {
-                if (L.more) lit12_step<kPred, true, kTab, true>(L, w32.data(), lut, T.lo, img.data(), dmy);
-                if (N.more) lit12_step<kPred, true, kTab, true>(N, w32.data(), lut, T.lo, img.data(), dmy);
+            if (pass == 0) {
+                olen0 = olen, ost0 = ost, img0 = img;
+            } else if (olen != olen0 || ost != ost0 || img != img0) {
+                if (bad < 5) printf("lanes tab %d: the fill at %zu depends on the dword before its window\n", kTab, f);
+                ++bad;
             }
-            // results as the kernel's: the first slot's status from its end position and the window
-            // (its dword pair is not kept), the second's from the walk
-            if (L.act) {
-                const uint32_t Eb = p0[u1] * 8u + 31u + nb[u1] * 8u;
-                olen[t1] = L.o - L.o0;
-                ost[t1] = L.st != HPK_OK ? L.st : residual_status(Eb - L.X, win_at(w32.data(), L.X - 31u));
-            }
-            if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
         }
         for (size_t t = 0; t < k; ++t) {
             std::vector<uint8_t> ref(cap[t] + 8);

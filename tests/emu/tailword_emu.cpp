@@ -171,7 +171,7 @@ static long run_lanes(const Lits& lits, std::mt19937_64& rng, long* slow_lanes, 
     long bad = 0;
     for (size_t f = 0; f < lits.size(); f += 128) {
         const size_t k = std::min<size_t>(128, lits.size() - f);
-        const uint32_t mis = 4 + rng() % 12;
+        const uint32_t mis = rng() % 16;  // (0: a literal at byte 0 of the window, the guard dword in front of it)
         std::vector<uint8_t> win(mis);
         std::vector<uint32_t> p0(k), nb(k), o0(k), cap(k);
         const uint32_t ofirst = 4 + rng() % 4;
@@ -184,65 +184,87 @@ static long run_lanes(const Lits& lits, std::mt19937_64& rng, long* slow_lanes, 
             cap[t] = nb[t] * 8 / 5;
             op += cap[t];
         }
-        win.resize(win.size() + 64, 0x5A);
-        std::vector<uint32_t> w32(win.size() / 4 + 4, 0);
-        for (size_t j = 0; j + 4 <= win.size(); j += 4)
-            w32[j / 4] = ((uint32_t)win[j] << 24) | ((uint32_t)win[j + 1] << 16) | ((uint32_t)win[j + 2] << 8) | win[j + 3];
+        // The window as the walk may read it and not a dword more, so that a host sanitizer sees the true edges: one guard
+        // dword in front (lit12_load reads the dword before the one holding X: w32[-1] for a literal at byte 0 of the
+        // window, which mis == 0 places there), the literals, and the two dwords a step reads ahead of the one holding X
+        // ((X >> 5) + 1 and + 2, X <= Eb). Bytes past the last literal are 0x5A.
+        const size_t nd = (win.size() * 8 + 31) / 32 + 3;
+        win.resize(nd * 4, 0x5A);
+        std::vector<uint32_t> store(1 + nd, 0);
+        uint32_t* const w32 = store.data() + 1;
+        for (size_t j = 0; j < nd; ++j)
+            w32[j] = ((uint32_t)win[4 * j] << 24) | ((uint32_t)win[4 * j + 1] << 16) | ((uint32_t)win[4 * j + 2] << 8) | win[4 * j + 3];
         std::vector<uint8_t> img(op + 256 + 64, 0xEE);
         const uint32_t dmy = op + 64 + 4;
         std::vector<uint32_t> olen(k), ost(k);
         const uint32_t* lut = T.lut13;
-        for (int lane = 63; lane >= 0; --lane) {
-            const uint32_t t1 = lane, t2 = 127 - lane;
-            auto load = [&](Lit12& Z, uint32_t tt) {
-                const uint32_t u = std::min<uint32_t>(tt, k - 1);
-                Z.act = tt < k;
-                Z.idx = tt;
-                Z.X = p0[u] * 8u + 31u;
-                Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
-                Z.o = Z.o0 = o0[u];
-                Z.st = HPK_OK;
-                Z.prog = false;
-                lit12_load(Z, w32.data());
-            };
-            Lit12 L, N;
-            load(L, t1);
-            bool body = L.Eb - L.X >= kMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            // the first literal waits as (aX, aO, aSt, aAct) and its tail word
-            const uint32_t aX = L.X, aO = L.o, aSt = L.st, aN = tail12_word(L);
-            const bool aAct = L.act;
-            *body_status += aSt != HPK_OK;
-            load(L, t2);
-            body = L.Eb - L.X >= kMin;
-            while (body) lit12_body<kPred, kTab>(L, w32.data(), lut, T.lo, img.data(), body);
-            N = L;
-            const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
-            L.X = aX, L.o = aO, L.st = aSt, L.act = aAct;  // (d0, d1, d2 stay the second literal's)
-            L.Eb = p0[u1] * 8u + 31u + (aAct ? nb[u1] * 8u : 0u);
-            L.o0 = o0[u1];
-            if (aSt != HPK_OK) L.Eb = L.X;
-            L.more = L.Eb - L.X >= 5u;
-            N.more = N.Eb - N.X >= 5u;
-            Tail12 TL, TN;
-            tail12_begin_saved(TL, aN, L.Eb - L.X, L.o);
-            tail12_begin(TN, N);
-            for (int s = 0; s < 4; ++s) {
-                tail12_look<kPred, kTab>(TL, lut, img.data(), dmy);
-                tail12_look<kPred, kTab>(TN, lut, img.data(), dmy);
+        // The guard dword's value must not reach a result (lit12_load's contract, hpk_walk.h): the fill runs twice, with it
+        // all zeros and all ones, and must give the same lengths, statuses and image, byte for byte.
+        std::vector<uint32_t> olen0, ost0;
+        std::vector<uint8_t> img0;
+        for (int pass = 0; pass < 2; ++pass) {
+            store[0] = pass ? 0xFFFFFFFFu : 0x00000000u;
+            img.assign(img.size(), 0xEE);
+            olen.assign(k, 0);
+            ost.assign(k, 0);
+            for (int lane = 63; lane >= 0; --lane) {
+                const uint32_t t1 = lane, t2 = 127 - lane;
+                auto load = [&](Lit12& Z, uint32_t tt) {
+                    const uint32_t u = std::min<uint32_t>(tt, k - 1);
+                    Z.act = tt < k;
+                    Z.idx = tt;
+                    Z.X = p0[u] * 8u + 31u;
+                    Z.Eb = Z.X + (Z.act ? nb[u] * 8u : 0u);
+                    Z.o = Z.o0 = o0[u];
+                    Z.st = HPK_OK;
+                    Z.prog = false;
+                    lit12_load(Z, w32);
+                };
+                Lit12 L, N;
+                load(L, t1);
+                bool body = L.Eb - L.X >= kMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                // the first literal waits as (aX, aO, aSt, aAct) and its tail word
+                const uint32_t aX = L.X, aO = L.o, aSt = L.st, aN = tail12_word(L);
+                const bool aAct = L.act;
+                if (pass == 0) *body_status += aSt != HPK_OK;
+                load(L, t2);
+                body = L.Eb - L.X >= kMin;
+                while (body) lit12_body<kPred, kTab>(L, w32, lut, T.lo, img.data(), body);
+                N = L;
+                const uint32_t u1 = std::min<uint32_t>(t1, k - 1);
+                L.X = aX, L.o = aO, L.st = aSt, L.act = aAct;  // (d0, d1, d2 stay the second literal's)
+                L.Eb = p0[u1] * 8u + 31u + (aAct ? nb[u1] * 8u : 0u);
+                L.o0 = o0[u1];
+                if (aSt != HPK_OK) L.Eb = L.X;
+                L.more = L.Eb - L.X >= 5u;
+                N.more = N.Eb - N.X >= 5u;
+                Tail12 TL, TN;
+                tail12_begin_saved(TL, aN, L.Eb - L.X, L.o);
+                tail12_begin(TN, N);
+                for (int s = 0; s < 4; ++s) {
+                    tail12_look<kPred, kTab>(TL, lut, img.data(), dmy);
+                    tail12_look<kPred, kTab>(TN, lut, img.data(), dmy);
+                }
+                const bool slowL = tail12_end<kTab>(TL, L);
+                L.more &= slowL;
+                N.more &= tail12_end<kTab>(TN, N);
+                if (pass == 0) *slow_lanes += (int)slowL;
+                if (slowL) lit12_load(L, w32);
+                for (int guard = 0; (L.more || N.more) && guard < 1000000; ++guard) {
+                    if (L.more) lit12_step<kPred, true, kTab, true>(L, w32, lut, T.lo, img.data(), dmy);
+                    if (N.more) lit12_step<kPred, true, kTab, true>(N, w32, lut, T.lo, img.data(), dmy);
+                }
+                if (slowL && L.st == HPK_OK) L.st = residual_status(L.Eb - L.X, win_at(w32, L.X - 31u));
+                if (L.act) olen[t1] = L.o - L.o0, ost[t1] = L.st;  // carried: no window read here
+                if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
             }
-            const bool slowL = tail12_end<kTab>(TL, L);
-            L.more &= slowL;
-            N.more &= tail12_end<kTab>(TN, N);
-            *slow_lanes += (int)slowL;
-            if (slowL) lit12_load(L, w32.data());
-            for (int guard = 0; (L.more || N.more) && guard < 1000000; ++guard) {
-                if (L.more) lit12_step<kPred, true, kTab, true>(L, w32.data(), lut, T.lo, img.data(), dmy);
-                if (N.more) lit12_step<kPred, true, kTab, true>(N, w32.data(), lut, T.lo, img.data(), dmy);
+            if (pass == 0) {
+                olen0 = olen, ost0 = ost, img0 = img;
+            } else if (olen != olen0 || ost != ost0 || img != img0) {
+                if (bad < 5) printf("lanes: the fill at %zu depends on the dword before its window\n", f);
+                ++bad;
             }
-            if (slowL && L.st == HPK_OK) L.st = residual_status(L.Eb - L.X, win_at(w32.data(), L.X - 31u));
-            if (L.act) olen[t1] = L.o - L.o0, ost[t1] = L.st;  // carried: no window read here
-            if (N.act) olen[t2] = N.o - N.o0, ost[t2] = lit12_status(N);
         }
         for (size_t t = 0; t < k; ++t) {
             std::vector<uint8_t> ref(cap[t] + 8);

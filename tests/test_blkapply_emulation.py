@@ -7,7 +7,8 @@ random and the scan's placed blocks, every truncation of the RFC 7541 App. C blo
 own placed cases) with a ring of the kernel's size and with a small one that the stories' insertions wrap many times
 and that defers more. The answers are blocks_apply_cases.ref_apply's, which tests/test_blocks_apply_cases.py pins to
 hpack_ref.Decoder: per block the headers resolved to bytes, the error and its detail; per decoder the blocks applied
-and the final table, entry by entry."""
+and the final table, entry by entry.
+The program is also built with -fsanitize=address,undefined and run stand-alone on the same case files."""
 
 import os
 import shutil
@@ -18,6 +19,7 @@ import pytest
 
 import blocks_apply_cases as ac
 import blocks_scan_cases as bc
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -65,20 +67,27 @@ def pairs(tokens):
     return [tuple(bytes.fromhex(x) for x in t.split(":")) for t in tokens]
 
 
-@pytest.mark.parametrize("ring", [2048, 128])
-def test_step_matches_ref_apply(emu, ring):
-    exe, d = emu
-    corp = ac.corpora(ring, 64)
-    decoders = [dec for name in sorted(corp) for dec in corp[name]]
-    assert len(decoders) > 3900
-    path = d / f"cases{ring}.bin"
-    write_cases(path, decoders, ring)
-    p = subprocess.run([exe, str(path), str(ring)], capture_output=True, text=True, timeout=600)
+_cases = {}
+
+
+def cases(d, ring):
+    """per ring size, made once: the case file both builds of the program read, its decoders, ref_apply's answer and
+    the tables after it"""
+    if ring not in _cases:
+        corp = ac.corpora(ring, 64)
+        decoders = [dec for name in sorted(corp) for dec in corp[name]]
+        assert len(decoders) > 3900
+        path = d / f"cases{ring}.bin"
+        write_cases(path, decoders, ring)
+        tabs = ac.fresh(decoders)
+        _cases[ring] = (str(path), decoders, ac.ref_apply(tabs, ring), tabs)
+    return _cases[ring]
+
+
+def check(p, ring, decoders, want, tabs):
     assert p.returncode == 0 and f"done: {len(decoders)} decoders" in p.stdout, p.stdout[-2000:] + p.stderr
     assert "#" not in p.stdout and "!" not in p.stdout and "\nV" not in p.stdout
     lines = iter(p.stdout.splitlines())
-    tabs = ac.fresh(decoders)
-    want = ac.ref_apply(tabs, ring)
     deferred = errors = 0
     for k, ((results, applied), (tab, blocks)) in enumerate(zip(want, tabs)):
         for b, (headers, error, detail) in enumerate(results):
@@ -93,3 +102,24 @@ def test_step_matches_ref_apply(emu, ring):
         assert pairs(x[5:]) == tab.entries, k
     assert errors > 500
     assert deferred >= (8 if ring == 2048 else 10)
+
+
+@pytest.mark.parametrize("ring", [2048, 128])
+def test_step_matches_ref_apply(emu, ring):
+    exe, d = emu
+    path, *rest = cases(d, ring)
+    check(subprocess.run([exe, path, str(ring)], capture_output=True, text=True, timeout=600), ring, *rest)
+
+
+@pytest.fixture(scope="module")
+def emu_san(emu):
+    return san_util.build_emu(emu[1], "blkapply_emu_san", san_util.ASAN + ["-Wall"], source="blkapply_emu", oracle=False)
+
+
+@pytest.mark.parametrize("ring", [2048, 128])
+def test_step_under_host_sanitizers(emu, emu_san, ring):
+    """The same program with ASan and UBSan, stand-alone, on the same case files and with the same checks."""
+    path, *rest = cases(emu[1], ring)
+    p = subprocess.run([emu_san, path, str(ring)], capture_output=True, text=True, timeout=600)
+    check(p, ring, *rest)
+    san_util.assert_no_reports(p)

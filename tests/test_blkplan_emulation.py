@@ -7,7 +7,8 @@ blocks_plan_cases.corpora() (the interop stories' header lists, the random lists
 collisions) with a ring of the kernel's size and with one of 128 records that the stories wrap many times and that
 defers more. The answers are blocks_plan_cases.ref_plan's, which tests/test_blocks_plan_cases.py pins to
 hpack_ref.Encoder: per header the kind, the index, the prefix octets and the three items resolved to bytes; per
-encoder the blocks planned and the final table, entry by entry."""
+encoder the blocks planned and the final table, entry by entry.
+The program is also built with -fsanitize=address,undefined and run stand-alone on the case files the runs above wrote."""
 
 import os
 import shutil
@@ -18,6 +19,7 @@ import pytest
 
 import blocks_apply_cases as ac
 import blocks_plan_cases as pc
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -60,18 +62,26 @@ def pairs(tokens):
     return [tuple(bytes.fromhex(x) for x in t.split(":")) for t in tokens]
 
 
-def run_emu(emu, encoders, ring, tag):
+_wants = {}
+
+
+def run_emu(emu, encoders, ring, tag, exe=None):
     """the emulation over `encoders`, checked against ref_plan on copies of the tables -> (the tables as the emulation
-    printed them, the deferred blocks, the planned headers)"""
-    exe, d = emu
+    printed them, the deferred blocks, the planned headers). exe: another build of the program, run on the case file
+    and against the answer that the call without it made under the same tag."""
+    d = emu[1]
     path = d / f"cases{tag}.bin"
-    write_cases(path, encoders, ring)
-    p = subprocess.run([exe, str(path), str(ring)], capture_output=True, text=True, timeout=600)
+    if exe is None:
+        write_cases(path, encoders, ring)
+        tabs = pc.fresh(encoders)
+        _wants[tag] = (pc.ref_plan(tabs, ring), tabs)
+    want, tabs = _wants[tag]
+    p = subprocess.run([exe or emu[0], str(path), str(ring)], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and f"done: {len(encoders)} encoders" in p.stdout, p.stdout[-2000:] + p.stderr
     assert "#" not in p.stdout and "!" not in p.stdout and "\nV" not in p.stdout
+    if exe is not None:
+        san_util.assert_no_reports(p)
     lines = iter(p.stdout.splitlines())
-    tabs = pc.fresh(encoders)
-    want = pc.ref_plan(tabs, ring)
     deferred = headers = 0
     after = []
     for k, ((results, planned), (tab, blocks, _)) in enumerate(zip(want, tabs)):
@@ -113,3 +123,20 @@ def test_step_matches_ref_plan(emu, ring):
     assert headers > 190000
     # the deferral cases' four blocks; with the small ring also the twelve search cases' and the two index cases' tables
     assert deferred >= (4 if ring == 2048 else 18)
+
+
+@pytest.fixture(scope="module")
+def emu_san(emu):
+    return san_util.build_emu(emu[1], "blkplan_emu_san", san_util.ASAN + ["-Wall"], source="blkplan_emu", oracle=False)
+
+
+@pytest.mark.parametrize("ring", [2048, 128])
+def test_step_under_host_sanitizers(emu, emu_san, ring):
+    """The same program with ASan and UBSan, stand-alone, on the same corpora and with the same checks."""
+    exe = emu_san
+    corp = pc.corpora(ring, 64, 64)
+    encoders = [enc for name in sorted(corp) for enc in corp[name]]
+    if ring not in _wants:  # (run alone: the unsanitized run writes the case file and makes the model's answer)
+        run_emu(emu, encoders, ring, ring)
+    _, deferred, headers = run_emu(emu, encoders, ring, ring, exe=exe)
+    assert headers > 190000 and deferred >= (4 if ring == 2048 else 18)

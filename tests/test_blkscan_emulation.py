@@ -6,7 +6,8 @@ prefix of the RFC 7541 App. C blocks, the seeded corruptions, the random blocks 
 The answers are blocks_scan_cases.ref_scan's, which tests/test_blocks_scan_cases.py pins to hpack_ref.Decoder. The
 program also checks that count and emit agree, and that no octet outside the block is read: through a checking
 accessor, and with the blob at the end of a buffer whose next page has no access, at all 4 dword alignments, with
-and without poison bytes after the block."""
+and without poison bytes after the block.
+The program is also built with -fsanitize=address,undefined and run stand-alone on the same case file."""
 
 import os
 import shutil
@@ -16,6 +17,7 @@ import subprocess
 import pytest
 
 import blocks_scan_cases as bc
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -40,25 +42,30 @@ def parse(line):
     return fields, strings
 
 
-def test_walk_matches_ref_scan(emu):
-    exe, d = emu
+@pytest.fixture(scope="module")
+def cases(emu):
+    """the case file both builds of the program read, its blocks, the placed cases among them (the first ones) and
+    ref_scan's answer per block"""
     placed = bc.placed()
     blocks = [b for _, b, _ in placed] + bc.rfc_prefixes() + [w for s in bc.corrupted_stories() for w in s]
     blocks += bc.random_blocks() + bc.interop_blocks()[::5]
     assert len(blocks) > 7000
-    path = d / "cases.bin"
+    path = emu[1] / "cases.bin"
     with open(path, "wb") as f:
         f.write(struct.pack("<I", len(blocks)))
         for w in blocks:
             f.write(struct.pack("<I", len(w)) + w)
-    p = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=300)
+    return str(path), blocks, placed, [bc.ref_scan(w) for w in blocks]
+
+
+def check(p, blocks, placed, wants):
     assert p.returncode == 0, p.stdout[-4000:] + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln and ln[0].isdigit()]
     assert len(lines) == len(blocks) and f"ok: 0 failures in {len(blocks)} cases" in p.stdout
     stages, errs = set(), set()
     for i, (w, ln) in enumerate(zip(blocks, lines)):
         got = parse(ln)
-        want = bc.ref_scan(w)
+        want = wants[i]
         assert got == (want[0], want[1]), f"block {i} ({w[:16].hex()}..., {len(w)} bytes): {got} for {want}"
         if i < len(placed):
             bc.check_expect(placed[i][0], w, got[0], got[1], placed[i][2])
@@ -67,3 +74,15 @@ def test_walk_matches_ref_scan(emu):
             errs.add(got[0][-1].err)
     assert stages == {bc.ST_INDEX, bc.ST_NAME, bc.ST_VALUE}
     assert errs == {bc.E_INT_TOO_MANY, bc.E_INT_SHORT, bc.E_STR_SHORT}
+
+
+def test_walk_matches_ref_scan(emu, cases):
+    check(subprocess.run([emu[0], cases[0]], capture_output=True, text=True, timeout=300), *cases[1:])
+
+
+def test_walk_under_host_sanitizers(emu, cases):
+    """The same program with ASan and UBSan, stand-alone, on the same case file and with the same checks."""
+    exe = san_util.build_emu(emu[1], "blkscan_emu_san", san_util.ASAN, source="blkscan_emu", oracle=False)
+    p = subprocess.run([exe, cases[0]], capture_output=True, text=True, timeout=300)
+    check(p, *cases[1:])
+    san_util.assert_no_reports(p)

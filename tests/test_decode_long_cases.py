@@ -11,7 +11,10 @@ Fix rounds. The truth moves one piece per round, so a stream that never resynchr
 to reach its terminal piece t (0-based): P - 2 for a literal walked to its end, which is what the clean and the
 foreign-symbol endings are. A literal with EOS at 3/4 has t = 3 P / 4, and the pieces behind t are ignored, so its
 bound is t - 1 (measured at P = 128: 94 to 125 rounds, at P = 1024: 766 to 1021). The stream of byte 10 with '0'
-resynchronises inside the lead (0 rounds, whatever stands in front of it): asserted as that."""
+resynchronises inside the lead (0 rounds, whatever stands in front of it): asserted as that.
+
+The replay is also built with -fsanitize=address,undefined and run stand-alone on the same case files: each literal's
+input then ends with its last 16-byte chunk, so a chunk read past the clamp is a report."""
 
 import os
 import shutil
@@ -21,6 +24,7 @@ import numpy as np
 import pytest
 
 import decode_long_cases as dc
+import san_util
 from hpk_util import oracle_decode_batch, pack
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -47,13 +51,15 @@ def geo():
     return g
 
 
-def replay(emu, lits, tab, lanes):
-    """the replay's line per literal as a dict of ints"""
-    exe, d = emu
+def replay(emu, lits, tab, lanes, exe=None):
+    """the replay's line per literal as a dict of ints (exe: another build of the program)"""
+    d = emu[1]
     path = str(d / f"cases_{tab}.bin")
     dc.write_emu_file(path, lits)
-    p = subprocess.run([exe, "--file", path, str(lanes), str(tab)], capture_output=True, text=True, timeout=600)
+    p = subprocess.run([exe or emu[0], "--file", path, str(lanes), str(tab)], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "ok: 0 mismatches" in p.stdout, p.stdout[-3000:] + p.stderr
+    if exe is not None:
+        san_util.assert_no_reports(p)
     rows = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("lit ")]
     assert len(rows) == len(lits)
     return [dict(zip(r[2:-1:2], map(int, r[3:-1:2]))) for r in rows]
@@ -151,6 +157,24 @@ def test_replay_of_the_batches_huge_literals(emu, geo):
     for tab in (2, 4):
         replay(emu, lits, tab, geo.block)
     replay(emu, [dc.case(n).lits[0] for n in dc.names("straddle30-")], 4, 64)
+
+
+@pytest.fixture(scope="module")
+def emu_san(emu):
+    return san_util.build_emu(emu[1], "emu_san", san_util.ASAN, source="emu")
+
+
+@pytest.mark.parametrize("tab", [2, 4])
+def test_huge_cases_replay_under_host_sanitizers(emu, emu_san, geo, tab):
+    """The same program with ASan and UBSan, stand-alone, on the case file of test_huge_cases_replay: every literal
+    decodes as the oracle does (the program's own check), with the status and the piece geometry the case states."""
+    names = list(dc.HUGE_SINGLE)
+    rows = dict(zip(names, replay(emu, [dc.case(n).lits[0] for n in names], tab, geo.block, exe=emu_san)))
+    for n in names:
+        r, c = rows[n], dc.case(n)
+        assert r["status"] == c.meta["status"], n
+        assert (r["P"], r["PB"]) == dc.huge_geometry(len(c.lits[0]), geo.block, geo.piece_min)[:2], n
+    assert rows["noresync-len5-64k-clean"]["rounds"] == 1023
 
 
 def test_placed_codes(geo, walks):

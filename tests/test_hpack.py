@@ -8,6 +8,7 @@ import random
 
 import pytest
 
+from hpack_cases import churn_streams
 from hpk_util import hpack_ref, load
 
 from loona_amd import hpack
@@ -201,33 +202,10 @@ def test_dynamic_table_churn_matches_restatement():
     all blocks in one call: the table's entry ring grows past its first 64 slots and its byte buffer
     is compacted many times (hpk_hdec's allocation-free table); every block's headers or first error
     equal decoder.rs's restatement (oracle/hpack_ref.py)."""
-    rng = random.Random(4096)
     pairs, want = [], []
-    for stream in range(6):
+    for blocks in churn_streams():  # (tests/hpack_cases.py: the stand-alone host driver decodes the same streams)
         d, r = hpack.Decoder(), hpack_ref.Decoder()
-        entries = 0
-        for _ in range(120):
-            blk = bytearray()
-            if rng.random() < 0.15:  # dynamic table size update (decoder.rs:538-554)
-                blk += hpack_ref.encode_integer(rng.choice([0, 100, 4096, 20000, 60000]), 5, 0x20)
-            for _ in range(rng.randrange(1, 24)):
-                op = rng.random()
-                if op < 0.55:  # literal with incremental indexing, new name
-                    nl = rng.choice([0, 1, 5, 12, 40, rng.randrange(0, 300)])
-                    vl = rng.choice([0, 3, 20, 100, rng.randrange(0, 5000)])
-                    blk += b"\x40" + hpack_ref.encode_integer(nl, 7, 0) + bytes(rng.randrange(97, 123) for _ in range(nl))
-                    blk += hpack_ref.encode_integer(vl, 7, 0) + bytes(rng.randrange(32, 127) for _ in range(vl))
-                    entries += 1
-                elif op < 0.75:  # literal with incremental indexing, indexed name
-                    idx = rng.randrange(1, 62) if rng.random() < 0.7 else rng.randrange(62, 65)
-                    vl = rng.randrange(0, 60)
-                    blk += hpack_ref.encode_integer(idx, 6, 0x40)
-                    blk += hpack_ref.encode_integer(vl, 7, 0) + bytes(rng.randrange(32, 127) for _ in range(vl))
-                    entries += 1
-                else:  # indexed field, sometimes past the table
-                    hi = 62 + min(entries, 400) + 3 if rng.random() < 0.05 else 65
-                    blk += hpack_ref.encode_integer(rng.randrange(1, hi), 7, 0x80)
-            w = bytes(blk)
+        for w in blocks:
             pairs.append((d, w))
             want.append(_ref_decode(r, w))
     got = hpack.decode_blocks(pairs)

@@ -7,13 +7,16 @@ alternating, or constant) choice between two source blobs; both sources at every
 empty literals longer than the window (kPackLds); literals longer than a tile (kPackTile); 1-7-byte literals so
 that nearly every 16-byte chunk mixes both sources (the program counts them); capacity cuts; a poisoned byte
 just outside each source's range. The result is compared with memcpy and every byte outside the written range
-with a canary. What it cannot cover (LDS, barriers, the scans) is tests/test_gpu_decode_strings.py's job."""
+with a canary. What it cannot cover (LDS, barriers, the scans) is tests/test_gpu_decode_strings.py's job.
+The program is also built with -fsanitize=address,undefined and run stand-alone."""
 
 import os
 import shutil
 import subprocess
 
 import pytest
+
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -34,3 +37,12 @@ def test_pack2_emulation_matches_memcpy(emu, seed):
     p = subprocess.run([emu, str(seed), "1"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout[-4000:] + p.stderr
     assert "ok: 0 mismatches" in p.stdout
+
+
+def test_pack2_emulation_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (another seed)."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("pack2_emu_san"), "pack2_emu_san", san_util.ASAN, source="pack2_emu", oracle=False)
+    p = subprocess.run([exe, "3", "1"], capture_output=True, text=True, timeout=300)
+    san_util.assert_clean(p)

@@ -7,13 +7,16 @@ when it is used up. The layouts put literal boundaries on the tile edges, a lite
 more empty and one-byte literals than the window holds, exact totals around the tile size, empty batches,
 misaligned source and destination bases and capacity cuts; the result is compared with memcpy and every
 byte outside the written range with a canary. What it cannot cover (LDS, barriers, the length scan) is
-tests/test_packed.py's job on the GPU."""
+tests/test_packed.py's job on the GPU.
+The program is also built with -fsanitize=address,undefined and run stand-alone."""
 
 import os
 import shutil
 import subprocess
 
 import pytest
+
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -34,3 +37,12 @@ def test_pack_emulation_matches_memcpy(emu, seed):
     p = subprocess.run([emu, str(seed), "2"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ok: 0 mismatches" in p.stdout
+
+
+def test_pack_emulation_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (another seed)."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("pack_emu_san"), "pack_emu_san", san_util.ASAN, source="pack_emu", oracle=False)
+    p = subprocess.run([exe, "3", "2"], capture_output=True, text=True, timeout=300)
+    san_util.assert_clean(p)

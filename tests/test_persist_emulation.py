@@ -14,7 +14,7 @@ from hpk_persist.h, where it has to stay) and the function it chooses, one lane 
 Every case: the oracle's status, length and bytes, and no byte outside the literal's region changed.
 Finding of c, modelled in the program and explained in its header: the lane walk reads up to three dwords past its
 33-dword input slot (in the kernel the next lane's first dwords); they never decide anything.
-The program is also a stand-alone target for a host sanitizer build (-fsanitize=address,undefined)."""
+The program is also built with -fsanitize=address,undefined and run stand-alone."""
 
 import os
 import re
@@ -24,6 +24,7 @@ import subprocess
 
 import pytest
 
+import san_util
 from hpk_util import load
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -108,3 +109,15 @@ def test_second_seed(persist_emu):
     p = subprocess.run([persist_emu, "2", "-"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ok: 0 mismatches" in p.stdout
+
+
+def test_persist_emulation_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (the second seed, without the error vectors: the program has
+    no smaller workload). Its slots are malloc'd at their exact sizes, so a read past one is a report."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("persist_emu_san"), "persist_emu_san", san_util.ASAN, source="persist_emu")
+    p = subprocess.run([exe, "2", "-"], capture_output=True, text=True, timeout=600)
+    san_util.assert_clean(p)
+    paths = nums(r"paths: empty (\d+) staged_bound (\d+) staged_bytes (\d+) global (\d+)", p.stdout)
+    assert all(x > 0 for x in paths), p.stdout

@@ -7,7 +7,8 @@ every window length from 0 up to its integer's length, with length == window, le
 bytes, a 5th octet with the continuation bit, and padded non-canonical integers. The answers are
 hpack_ref.decode_integer's and decode_string's on the same window. The program also checks that no byte outside
 the window's intersection with the blob is read: through a checking accessor, and with the blob at the end of a
-buffer whose next page has no access, at all 4 dword alignments, with and without poison bytes after the window."""
+buffer whose next page has no access, at all 4 dword alignments, with and without poison bytes after the window.
+The program is also built with -fsanitize=address,undefined and run stand-alone on the same case file."""
 
 import os
 import shutil
@@ -17,6 +18,7 @@ import subprocess
 import pytest
 
 import decode_strings_cases as dc
+import san_util
 from hpk_util import hpack_ref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,16 +51,20 @@ def reference(window):
     return (dc.OK, window[0] >> 7, used, ln, consumed)
 
 
-def test_strparse_matches_hpack_ref(emu):
-    exe, d = emu
+@pytest.fixture(scope="module")
+def cases(emu):
+    """the case file both builds of the program read, and its windows"""
     shapes = dc.prefix_shapes()
     assert len(shapes) > 150
-    path = d / "cases.bin"
+    path = emu[1] / "cases.bin"
     with open(path, "wb") as f:
         f.write(struct.pack("<I", len(shapes)))
         for _, w in shapes:
             f.write(struct.pack("<I", len(w)) + w)
-    p = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+    return str(path), shapes
+
+
+def check(p, shapes):
     assert p.returncode == 0, p.stdout[-4000:] + p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln and ln[0].isdigit()]
     assert len(lines) == len(shapes) and f"ok: 0 failures in {len(shapes)} cases" in p.stdout
@@ -69,3 +75,15 @@ def test_strparse_matches_hpack_ref(emu):
         assert got == want, f"{what} ({w[:8].hex()}..., {len(w)} bytes): {got} for {want}"
         seen.add(want[0])
     assert seen == {dc.OK, dc.TOO_MANY, dc.INT_SHORT, dc.STR_SHORT}
+
+
+def test_strparse_matches_hpack_ref(emu, cases):
+    check(subprocess.run([emu[0], cases[0]], capture_output=True, text=True, timeout=120), cases[1])
+
+
+def test_strparse_under_host_sanitizers(emu, cases):
+    """The same program with ASan and UBSan, stand-alone, on the same case file and with the same checks."""
+    exe = san_util.build_emu(emu[1], "strparse_emu_san", san_util.ASAN, source="strparse_emu", oracle=False)
+    p = subprocess.run([exe, cases[0]], capture_output=True, text=True, timeout=300)
+    check(p, cases[1])
+    san_util.assert_no_reports(p)

@@ -11,7 +11,9 @@ tests/test_walk_emulation.py does for the walk, and checks:
      sequences) never take the fallback;
   c. whole literals: the wave kernel's lane protocol (body steps, masked tails, checked steps for the slow
      lanes) on the walk emulation's literal mix, exact-bound regions back to back, against the oracle.
-The program is also a stand-alone target for a host sanitizer build (-fsanitize=address,undefined)."""
+The program is also built with -fsanitize=address,undefined and run stand-alone: each fill's window is an allocation of
+exactly the dwords the walk may read, one guard dword in front included, and every fill runs with that dword all zeros
+and all ones (lit12_load's contract, hpk_walk.h)."""
 
 import os
 import re
@@ -19,6 +21,8 @@ import shutil
 import subprocess
 
 import pytest
+
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -68,3 +72,19 @@ def test_masked_tail_second_seed(tail_emu):
     p = subprocess.run([tail_emu, "2", "2", "20000"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ok: 0 mismatches, 0 valid tails slow" in p.stdout
+
+
+def test_masked_tail_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (the second seed's workload)."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("tail_emu_san"), "tail_emu_san", san_util.ASAN, source="tail_emu")
+    p = subprocess.run([exe, "2", "2", "20000"], capture_output=True, text=True, timeout=300)
+    san_util.assert_clean(p, "ok: 0 mismatches, 0 valid tails slow")
+    m = re.search(r"tails alone: (\d+) cases, (\d+) slow, (\d+) mismatches", p.stdout)
+    assert m and int(m.group(1)) >= 2 * 32 * (2**17 - 1) + 12 * 20000 and int(m.group(3)) == 0, p.stdout
+    m = re.search(r"whole literals: (\d+) literals, (\d+) slow tails, (\d+) mismatches", p.stdout)
+    assert m and int(m.group(1)) >= 2 * 6000 and int(m.group(3)) == 0, p.stdout  # (two rounds of 3,000 literals per table)
+    assert int(m.group(2)) > 0, "the mix never took the checked fallback"
+    ms = re.findall(r"valid tails tab (\d): (\d+) cases, (\d+) slow", p.stdout)
+    assert len(ms) == 2 and all(int(cases) > 100000 and int(slow) == 0 for _, cases, slow in ms), p.stdout

@@ -9,7 +9,9 @@ tests/test_walk13_emulation.py does, and checks under table kind 4:
      the body set one;
   b. whole literals through the lane protocol as the kernel runs it now (the first literal's dwords are gone when
      its tail starts; only its slow lanes reload them), exact-bound regions back to back, against the oracle.
-The program is also a stand-alone target for a host sanitizer build (-fsanitize=address,undefined)."""
+The program is also built with -fsanitize=address,undefined and run stand-alone: each fill's window is an allocation of
+exactly the dwords the walk may read, one guard dword in front included, and every fill runs with that dword all zeros
+and all ones (lit12_load's contract, hpk_walk.h)."""
 
 import os
 import re
@@ -17,6 +19,8 @@ import shutil
 import subprocess
 
 import pytest
+
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -55,3 +59,18 @@ def test_whole_literals_match_the_oracle(run1):
     assert n >= 14000 and bad == 0, run1.stdout
     assert slow > 0 and body > 0, "the mix never took the slow path or never ended in a body"
     assert "ok: 0 mismatches" in run1.stdout
+
+
+def test_tailword_emulation_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (another seed, 20k random patterns per length)."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("tailword_emu_san"), "tailword_emu_san", san_util.ASAN, source="tailword_emu")
+    p = subprocess.run([exe, "2", "20000"], capture_output=True, text=True, timeout=300)
+    san_util.assert_clean(p)
+    m = re.search(r"tails alone: (\d+) cases \((\d+) patterns of 0\.\.16 bits, (\d+) random\), (\d+) slow, (\d+) mismatches",
+                  p.stdout)
+    assert m and int(m.group(2)) == 2**17 - 1 and int(m.group(3)) >= 14 * 20000 and int(m.group(4)) > 0 and int(m.group(5)) == 0, p.stdout
+    m = re.search(r"whole literals: (\d+) literals, (\d+) slow first tails, (\d+) body statuses, (\d+) mismatches", p.stdout)
+    assert m and int(m.group(1)) >= 14000 and int(m.group(4)) == 0, p.stdout
+    assert int(m.group(2)) > 0 and int(m.group(3)) > 0, "the mix never took the slow path or never ended in a body"

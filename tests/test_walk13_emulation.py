@@ -11,7 +11,9 @@ lit12_tail and the checked step:
   c. whole literals against the oracle, through the wave kernel's lane protocol and through the checked step
      alone: code bits sweeping 24..48 (the body-min boundary at 29..32), literals made only of the 13-bit pairs
      (6+7, 7+6, 5+8, 8+5) and of the six 13-bit codes (symbols 0, $, @, [, ], ~), and the tail emulation's mix.
-The program is also a stand-alone target for a host sanitizer build (-fsanitize=address,undefined)."""
+The program is also built with -fsanitize=address,undefined and run stand-alone: each fill's window is an allocation of
+exactly the dwords the walk may read, one guard dword in front included, and every fill runs with that dword all zeros
+and all ones (lit12_load's contract, hpk_walk.h)."""
 
 import os
 import re
@@ -19,6 +21,8 @@ import shutil
 import subprocess
 
 import pytest
+
+import san_util
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -63,3 +67,22 @@ def test_whole_literals_match_the_oracle(run1):
     assert int(m.group(2)) >= 25 * 400 and int(m.group(3)) >= 3000 and int(m.group(5)) == 0, run1.stdout
     assert int(m.group(4)) > 0, "the mix never took the checked fallback"
     assert "ok: 0 mismatches, 0 valid tails slow" in run1.stdout
+
+
+def test_walk13_emulation_under_host_sanitizers(tmp_path_factory):
+    """The same program with ASan and UBSan, stand-alone (another seed, 20k random patterns per length)."""
+    if not san_util.have_compilers():
+        pytest.skip("no host C/C++ compiler")
+    exe = san_util.build_emu(tmp_path_factory.mktemp("walk13_emu_san"), "walk13_emu_san", san_util.ASAN, source="walk13_emu")
+    p = subprocess.run([exe, "2", "20000"], capture_output=True, text=True, timeout=300)
+    san_util.assert_clean(p, "ok: 0 mismatches, 0 valid tails slow")
+    m = re.search(r"tails alone: (\d+) cases \((\d+) patterns of 0\.\.18 bits, (\d+) random, (\d+) long-code\), (\d+) slow, "
+                  r"(\d+) mismatches", p.stdout)
+    assert m and int(m.group(2)) == 2**19 - 1 and int(m.group(3)) >= 12 * 20000 and int(m.group(6)) == 0, p.stdout
+    assert int(m.group(4)) > 0 and int(m.group(5)) > 0, p.stdout
+    m = re.search(r"valid tails: (\d+) cases, (\d+) slow", p.stdout)
+    assert m and int(m.group(1)) > 100000 and int(m.group(2)) == 0, p.stdout
+    m = re.search(r"whole literals: (\d+) literals \((\d+) swept, (\d+) of 13-bit pairs and codes\), (\d+) slow tails, "
+                  r"(\d+) mismatches", p.stdout)
+    assert m and int(m.group(2)) >= 25 * 400 and int(m.group(3)) >= 3000 and int(m.group(5)) == 0, p.stdout
+    assert int(m.group(4)) > 0, "the mix never took the checked fallback"
