@@ -3,7 +3,7 @@
 // crates/loona-hpack/src/lib.rs:43-289) over the records hpk_scan_blocks left and the results
 // hpk_decode_strings_packed left for its string list. No byte of any string is touched: a name or a value is a
 // reference (offset, length) into one arena the caller defines, a table entry is an hpk_header of such references,
-// and so is an emitted header. The order of the checks is apply_block_dev's (hpk_hpack.cpp), which states the
+// and so is an emitted header. The order of the checks is apply_block's (hpk_hdec.cpp, the host's one apply pass), which states the
 // reference's precedence.
 //
 // Two steps:
@@ -148,7 +148,7 @@ __device__ __forceinline__ Step fail(Blk& b, uint32_t error, uint32_t detail) {
     return kStop;
 }
 
-// One record against the table, apply_block_dev's order. kEmit: *out is the block's next header (b.n_headers counts
+// One record against the table, apply_block's order. kEmit: *out is the block's next header (b.n_headers counts
 // it); kStop: b holds the block's error and nothing after this record is applied.
 template <class Tab, class SP>
 __device__ __forceinline__ Step apply_record(Tab& t, SP stat, uint32_t static_base, const Rec& r, Blk& b, hpk_header* out) {

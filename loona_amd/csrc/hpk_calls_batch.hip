@@ -143,7 +143,7 @@ static int run_batch(launch_fn fn, hpk_ctx* c, const uint8_t* in_blob, size_t in
     return chunks ? host_end(c) : HPK_E_OK;
 }
 
-// The block decoder's form (hpk_hpack.cpp): a trusted host batch started here, its chunks' results
+// The block decoder's form (hpk_hdec.cpp): a trusted host batch started here, its chunks' results
 // waited for one by one (so the caller applies chunk j's blocks while later chunks still decode),
 // then finished. Not part of the C ABI.
 int hpk_decode_host_begin(hpk_ctx* c, const uint8_t* in_blob, size_t in_cap, const uint32_t* in_off, uint32_t n,

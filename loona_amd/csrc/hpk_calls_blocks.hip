@@ -1,5 +1,5 @@
 // hpk_calls_blocks.hip — the header-block entry points of the C ABI (include/hpk.h): scan, apply and plan, and the
-// block codec's device paths (hpk_hpack.cpp calls them).
+// block codec's device paths (hpk_hdec.cpp and hpk_henc.cpp call them).
 #include <stdlib.h>
 
 #include <chrono>
@@ -209,7 +209,7 @@ extern "C" int hpk_plan_blocks(hpk_ctx* c, uint8_t* arena, size_t arena_cap, uin
     return hpk_call_end(c, flags);
 }
 
-// The block encoder's device-plan path (hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE; not in the C ABI): the caller has
+// The block encoder's device-plan path (hpk_henc.cpp, HPK_BLOCK_PLAN_DEVICE; not in the C ABI): the caller has
 // checked the inputs, so a void encoder here is a failure. One upload of the arena below the prefix area and of the
 // records; the two plan kernels; the ordered pack of the 3 nh items into a contiguous blob;
 // hpk_encode_strings_packed's steps with the item policies; the offsets at the block boundaries; then the tables,
@@ -283,7 +283,7 @@ int hpk_plan_device(hpk_ctx* c, hpk_planjob* job) {
     return HPK_E_OK;
 }
 
-// The block decoder's device-scan path (hpk_hpack.cpp, HPK_BLOCK_SCAN_DEVICE; not in the C ABI): block_off is
+// The block decoder's device-scan path (hpk_hdec.cpp, HPK_BLOCK_SCAN_DEVICE; not in the C ABI): block_off is
 // non-decreasing (the caller's check). The blocks and block_off go up once as they are; the count pass and the
 // scans run and the two totals come back (the pipeline's one wait before its end); the outputs are sized by them;
 // the emit pass and hpk_decode_strings_packed's steps over every listed string follow; then the field records,

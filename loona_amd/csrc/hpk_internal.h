@@ -1,4 +1,4 @@
-// hpk_internal.h — declarations shared between the host units of libhpk (hpk_cpu.cpp, hpk_hpack.cpp) and its
+// hpk_internal.h — declarations shared between the host units of libhpk (hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp) and its
 // device half (hpk_ctx.hip and the hpk_calls_*.hip call layer). Not part of the C ABI.
 #pragma once
 #include <stddef.h>
@@ -23,7 +23,7 @@ int hpk_host_chunk_wait(hpk_ctx* c, int j);
 int hpk_decode_host_end(hpk_ctx* c);
 int hpk_ctx_max_chunks();
 
-// The block decoder's device-scan path (hpk_calls_blocks.hip: hpk_blocks_device; used by hpk_hpack.cpp): what it leaves
+// The block decoder's device-scan path (hpk_calls_blocks.hip: hpk_blocks_device; used by hpk_hdec.cpp): what it leaves
 // in the context's page-locked area, valid until the context's next block call.
 struct hpk_blkdev {
     const hpk_field* fields;
@@ -61,7 +61,7 @@ struct hpk_applyplan {
 int hpk_blocks_device(hpk_ctx* c, const uint8_t* blocks, const uint32_t* block_off, uint32_t nblocks, hpk_blkdev* o,
                       hpk_applyplan* plan = nullptr);
 
-// The block encoder's device-plan path (hpk_calls_blocks.hip: hpk_plan_device; used by hpk_hpack.cpp, HPK_BLOCK_PLAN_DEVICE):
+// The block encoder's device-plan path (hpk_calls_blocks.hip: hpk_plan_device; used by hpk_henc.cpp, HPK_BLOCK_PLAN_DEVICE):
 // the host lays out hpk_plan_blocks' inputs, the device plans, gathers the items with the ordered pack and codes them
 // with hpk_encode_strings_packed's steps. Everything is on the host when it returns HPK_E_OK.
 struct hpk_planjob {

@@ -72,6 +72,29 @@ static inline hpk_lay_strdec hpk_layout_strdec(size_t dev_in, size_t n, size_t d
     return l;
 }
 
+// The block decoder's Huffman batch (hpk_hdec.cpp), in the page-locked area: in | dec | in_off | out_off | out_len |
+// status. Both blobs carry the 16 bytes of slack; out_len's region is as wide as the offsets' n + 1 entries, and the
+// n status bytes end the buffer.
+struct hpk_lay_hdecbatch {
+    hpk_at<uint8_t> in, dec, st;
+    hpk_at<uint32_t> in_off, out_off, len;
+    size_t bytes;
+    size_t in_cap() const { return dec.at - in.at; }  // the blobs' capacities, slack included
+    size_t dec_cap() const { return in_off.at - dec.at; }
+};
+static inline hpk_lay_hdecbatch hpk_layout_hdecbatch(size_t tot, size_t otot, size_t n) {
+    hpk_carve k;
+    hpk_lay_hdecbatch l;
+    l.in = k.blob(tot);
+    l.dec = k.blob(otot);
+    l.in_off = k.take<uint32_t>(n + 1);
+    l.out_off = k.take<uint32_t>(n + 1);
+    l.len = k.take<uint32_t>(n + 1);
+    l.st = {k.end};
+    l.bytes = k.end + n + 16;
+    return l;
+}
+
 // bs_stage. The head, all that the block decoder's device-scan path keeps there: blocks | block_off | field_off |
 // str_blk_off | status. The block scan's host form has its lists behind it: fields | str_off | str_end.
 struct hpk_lay_blkhead {

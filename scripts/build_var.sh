@@ -15,6 +15,7 @@ for u in $UNITS; do
 done
 wait
 for u in $UNITS; do [ -s $T/$u.o ] || { echo "$u failed"; exit 1; }; done
-make -s hpk_cpu.o hpk_hpack.o hpk_h2.o
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libhpk_$NAME.so hpk_cpu.o hpk_hpack.o hpk_h2.o $OBJS
+HOST=$(sed -n 's/^HOST := //p' Makefile)
+make -s $HOST
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libhpk_$NAME.so $HOST $OBJS
 echo built loona_amd/libhpk_$NAME.so

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Sanitizer builds of the host code, CPU only (no GPU sanitizer exists on this pool):
-#   asan  hpk_cpu.cpp, hpk_hpack.cpp, hpk_h2.cpp and the oracle with -fsanitize=address,undefined
+#   asan  hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp, hpk_h2.cpp and the oracle with -fsanitize=address,undefined
 #   tsan  the same host sources with -fsanitize=thread (the 16-thread pool of the block decoder, the
 #         threaded CPU batch paths, the fork handling)
 # Each links the unsanitized device objects (hpk_ctx/decode/encode, built by the Makefile) into
@@ -16,10 +16,10 @@ DEV="$CS/hpk_ctx.o $CS/hpk_decode.o $CS/hpk_encode.o"
 HIPLIB="-L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lamdhip64"
 build() {  # kind flags
   local k=$1 f=$2 T=/tmp/hpk_san_$1; mkdir -p $T
-  for s in hpk_cpu hpk_hpack hpk_h2; do
+  for s in hpk_cpu hpk_hdec hpk_henc hpk_h2; do
     g++ -std=c++17 -O1 -g -fPIC -fno-omit-frame-pointer $f -I/opt/rocm/include -c $CS/$s.cpp -o $T/$s.o
   done
-  g++ -shared -fPIC $f -o loona_amd/libhpk_$k.so $T/hpk_cpu.o $T/hpk_hpack.o $T/hpk_h2.o $DEV $HIPLIB -lpthread
+  g++ -shared -fPIC $f -o loona_amd/libhpk_$k.so $T/hpk_cpu.o $T/hpk_hdec.o $T/hpk_henc.o $T/hpk_h2.o $DEV $HIPLIB -lpthread
   echo "built loona_amd/libhpk_$k.so"
 }
 run() {  # kind runtime options-var

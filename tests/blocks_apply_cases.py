@@ -2,7 +2,7 @@
 
 ref_apply is a Python model of the call: per decoder a table of (name, value) entries, newest first, and the
 decoder's blocks in order; per block blocks_scan_cases.ref_scan's records and the block's strings decoded by
-hpack_ref, applied in the order hpk_hpack.cpp's apply_block_dev states; and the deferral rule for a given ring size
+hpack_ref, applied in the order hpk_hdec.cpp's apply_block states; and the deferral rule for a given ring size
 (lim = min(ring, the table's cap)). Names and values are bytes here, where the library moves references into an
 arena; the tests resolve the library's references before they compare. tests/test_blocks_apply_cases.py pins
 ref_apply to hpack_ref.Decoder; the emulation and the GPU tests compare the real step with it."""
@@ -77,7 +77,7 @@ def decode_strings(block, strings):
 
 
 def ref_apply_block(tab, fields, strs, static):
-    """apply_block_dev: -> (headers, error, detail), the headers those emitted before the first error"""
+    """apply_block over the device scan's records: -> (headers, error, detail), the headers those emitted before the first error"""
     out = []
     last_update = False
     for f in fields:

@@ -28,6 +28,10 @@ int main() {
             const hpk_lay_strdec l = hpk_layout_strdec(a[0], a[1], a[2], a[3] != 0);
             PUT(l, in), PUT(l, off), PUT(l, end), PUT(l, ooff), PUT(l, len), PUT(l, con), PUT(l, st), PUT(l, out);
             bytes = l.bytes;
+        } else if (!strcmp(what, "hdecbatch") && got == 4) {
+            const hpk_lay_hdecbatch l = hpk_layout_hdecbatch(a[0], a[1], a[2]);
+            PUT(l, in), PUT(l, dec), PUT(l, in_off), PUT(l, out_off), PUT(l, len), PUT(l, st);
+            bytes = l.bytes;
         } else if (!strcmp(what, "blkhead") && got == 3) {
             const hpk_lay_blkhead l = hpk_layout_blkhead(a[0], a[1]);
             PUT(l, in), PUT(l, boff), PUT(l, foff), PUT(l, soff), PUT(l, st);

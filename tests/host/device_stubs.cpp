@@ -1,5 +1,5 @@
 // device_stubs.cpp — the device half of libhpk as the stand-alone host driver sees it (tests/host/host_driver.cpp,
-// tests/test_host_sanitizers.py): the host units hpk_cpu.cpp, hpk_hpack.cpp and hpk_h2.cpp are compiled by themselves
+// tests/test_host_sanitizers.py): the host units hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp and hpk_h2.cpp are compiled by themselves
 // under a host sanitizer, and the symbols they take from hpk_ctx.hip and the hpk_calls_*.hip call layer are defined
 // here instead.
 //

@@ -1,6 +1,6 @@
-// host_driver.cpp — a stand-alone program around the host codec of libhpk (hpk_cpu.cpp, hpk_hpack.cpp, hpk_h2.cpp), for
+// host_driver.cpp — a stand-alone program around the host codec of libhpk (hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp, hpk_h2.cpp), for
 // builds under a host sanitizer (tests/test_host_sanitizers.py builds it plain, with ASan + UBSan and with TSan, each
-// time together with the three host units and tests/host/device_stubs.cpp; libhpk.so is not linked).
+// time together with the host units and tests/host/device_stubs.cpp; libhpk.so is not linked).
 //
 //   host_driver CASEFILE
 //

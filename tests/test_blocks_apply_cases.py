@@ -1,7 +1,7 @@
 """blocks_apply_cases.ref_apply pinned to the oracle (no GPU, no library).
 
 ref_apply applies blocks_scan_cases.ref_scan's records and hpack_ref's decoded strings against a table of its own,
-in the order hpk_hpack.cpp's apply_block_dev states. Here, with a ring too large to defer anything, it must
+in the order hpk_hdec.cpp's apply_block states. Here, with a ring too large to defer anything, it must
 reproduce hpack_ref.Decoder on every corpus of blocks_apply_cases.corpora(): the headers of a block that decodes,
 the first error of one that does not, and after every block the table, entry by entry, and its limit. The placed
 cases must also reach the edges they name, and the deferral rule must give the counts worked out for the issue."""

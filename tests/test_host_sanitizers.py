@@ -1,7 +1,7 @@
-"""The host codec (hpk_cpu.cpp, hpk_hpack.cpp, hpk_h2.cpp) under ASan + UBSan and under TSan, stand-alone (no GPU needed).
+"""The host codec (hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp, hpk_h2.cpp) under ASan + UBSan and under TSan, stand-alone (no GPU needed).
 
 tests/host/host_driver.cpp is a program of its own around the C ABI (include/hpk.h); it is built here three ways (plain
--O2, -fsanitize=address,undefined, -fsanitize=thread), each time together with the three host sources and with
+-O2, -fsanitize=address,undefined, -fsanitize=thread), each time together with the host sources and with
 tests/host/device_stubs.cpp in place of the device half: libhpk.so is not linked, nothing is loaded into python, and the
 driver only ever passes ctx == NULL (a device stub that is reached aborts). The case files (tests/host_cases.py) carry
 the inputs of the suite's other tests and the expected results from oracle/hpack_ref.py and the C oracle; the driver
@@ -14,7 +14,7 @@ hands every input to the library as an exact-size heap copy and checks every res
   threads  four callers at once, each decoding (encoding) >= 1,024 blocks per call on its own decoders: one owns the
            process-wide pool, the others spawn their own threads, all share hpk_blocks_out_free's kept buffers;
   fork     a pooled call, fork(), the same call in the child (ASan build and plain build only).
-What this cannot cover are the ctx != NULL branches of hpk_hpack.cpp: they need the device (the GPU tests)."""
+What this cannot cover are the ctx != NULL branches of hpk_hdec.cpp and hpk_henc.cpp: they need the device (the GPU tests)."""
 
 import os
 import re
@@ -30,7 +30,7 @@ import san_util
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "host", "host_driver.cpp"), os.path.join(HERE, "host", "device_stubs.cpp")] + \
-    [os.path.join(REPO, "loona_amd", "csrc", f) for f in ("hpk_cpu.cpp", "hpk_hpack.cpp", "hpk_h2.cpp")]
+    [os.path.join(REPO, "loona_amd", "csrc", f) for f in ("hpk_cpu.cpp", "hpk_hdec.cpp", "hpk_henc.cpp", "hpk_h2.cpp")]
 CALLERS, ROUNDS = 4, 3
 
 
@@ -42,7 +42,7 @@ def workdir(tmp_path_factory):
 
 
 def build(workdir, name, flags):
-    """the driver, the stubs and the three host sources, every one compiled here with the same flags"""
+    """the driver, the stubs and the host sources, every one compiled here with the same flags"""
     exe = str(workdir / name)
     subprocess.check_call(["g++", "-std=c++17", san_util.opt(flags), "-Wall", *flags, *SOURCES, "-o", exe, "-lpthread"])
     return exe
@@ -152,7 +152,7 @@ def test_plain_build_and_coverage(plain, files):
     quietly shrink): every hpk_block_error the C ABI can return, every hpk_h2_error, all three Huffman error statuses as
     a block's detail, and in the threaded mode calls of >= 1,024 blocks by callers that overlapped.
     HPK_BLK_INT_VALUE_TOO_LARGE is unused by the reference; HPK_BLK_INT_INVALID_PREFIX cannot occur either: every
-    prefix decode_integer is called with is a constant between 4 and 7 (hpk_hpack.cpp: scan_fields, scan_string)."""
+    prefix decode_integer is called with is a constant between 4 and 7 (hpk_hdec.cpp: scan_block, scan_string)."""
     blk, h2, detail = {}, {}, {}
     for name in ("codec", "frames", "threads", "fork"):
         p, n = run(plain, files[name])

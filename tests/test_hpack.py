@@ -71,7 +71,7 @@ def test_interop_stories_one_batch():
 
 def test_interop_stories_any_thread_count(monkeypatch):
     """The same batch on 1, 3 and 16 host threads: decoders are placed on the apply threads by hash
-    buckets balanced on the scanned work (hpk_hpack.cpp), each decoder's blocks in order on one
+    buckets balanced on the scanned work (hpk_hdec.cpp), each decoder's blocks in order on one
     thread, so every count gives the reference's headers."""
     pairs, want = [], []
     stories = list(_stories())

@@ -2,7 +2,8 @@
 
 tests/emu/layout_emu.cpp includes the REAL hpk_layout.h and prints every layout for the argument tuples below. Each
 is compared, offset by offset and in `bytes`, with the arithmetic the call code carried itself before the helper
-(hpk_ctx.hip at commit cc195cc, restated in OLD below with its line ranges): the layouts are byte for byte the same.
+(hpk_ctx.hip at commit cc195cc and, for the block decoder's batch area, hpk_hpack.cpp at commit 8b25017, restated in OLD
+below with their line ranges): the layouts are byte for byte the same.
 Independently of those formulas every layout must also be sound: each region on a 16-byte boundary, the regions in
 order and disjoint and each at least its element size times the count its call moves, a staged input followed by 16
 bytes of slack, and `bytes` at least 16 past the last region's end.
@@ -136,7 +137,17 @@ def old_plan(arena_cap, nh, nb, ne, nent, in_cap, out_cap):  # hpk_plan_device, 
                  boff=at_boff, out=at_out), at_out + out_cap + 16)
 
 
-OLD = dict(strings=old_strings, strdec=old_strdec, blkscan=old_blkscan, blkhead=old_blkhead, blkout=old_blkout, blkpin=old_blkpin,
+# What hpk_hpack.cpp computed at 8b25017 (hpk_hdec_decode_blocks, lines 1077-1087): out_len's region as wide as the
+# offsets' (off_b), the n status bytes at the buffer's end.
+def old_hdecbatch(tot, otot, n):
+    in_b, dec_b, off_b = up16(tot + 16), up16(otot + 16), up16(4 * (n + 1))
+    at_in_off = in_b + dec_b
+    at_st = at_in_off + 3 * off_b
+    return (dict(**{"in": 0}, dec=in_b, in_off=at_in_off, out_off=at_in_off + off_b, len=at_in_off + 2 * off_b, st=at_st),
+            in_b + dec_b + 3 * off_b + n + 16)
+
+
+OLD = dict(hdecbatch=old_hdecbatch, strings=old_strings, strdec=old_strdec, blkscan=old_blkscan, blkhead=old_blkhead, blkout=old_blkout, blkpin=old_blkpin,
            blkapply=old_blkapply, plan=old_plan)
 
 
@@ -146,6 +157,9 @@ def regions(what, a):
     if what == "strings":
         b, n, dcap = a
         return [("in", 1, b), ("ioff", 4, n + 1), ("ooff", 4, n + 1), ("len", 4, n), ("pol", 1, n), ("st", 1, n), ("out", 1, dcap)], ["in"]
+    if what == "hdecbatch":  # (both blobs carry the slack: the decode's stores may run past a string's bound)
+        tot, otot, n = a
+        return [("in", 1, tot), ("dec", 1, otot), ("in_off", 4, n + 1), ("out_off", 4, n + 1), ("len", 4, n), ("st", 1, n)], ["in", "dec"]
     if what == "strdec":
         b, n, dcap, mirror = a
         r = [("in", 1, b), ("off", 4, n + 1 if mirror else n), ("end", 4, n), ("ooff", 4, n + 1), ("len", 4, n), ("con", 4, n), ("st", 1, n),
@@ -181,6 +195,7 @@ def regions(what, a):
 def tuples():
     P = itertools.product
     t = [("strings", a) for a in P(SIZES, COUNTS, SIZES)]
+    t += [("hdecbatch", a) for a in P(SIZES, SIZES, (0,) + COUNTS)]
     t += [("strdec", a) for a in P(SIZES, COUNTS, SIZES, (0, 1))]
     t += [("blkhead", a) for a in P(SIZES, COUNTS)]
     t += [("blkscan", a) for a in P(SIZES, COUNTS, (0, 1, 4, 5), (0, 1, 4, 5))]
@@ -189,7 +204,7 @@ def tuples():
     t += [("blkapply", a) for a in P((0, 1, 3, 4), COUNTS, (0, 1, 5), (0, 1, 3))]
     t += [("plan", a) for a in P(SIZES, COUNTS, (1, 3), (1, 4, 5), (0, 1), (0, 15, 17), (1, 16))]
     # the largest counts the callers admit
-    t += [("strings", (HI_MAX, N_MAX, HI_MAX)), ("strdec", (HI_MAX, N_MAX, HI_MAX, 0)), ("strdec", (HI_MAX, N_MAX, HI_MAX, 1)),
+    t += [("hdecbatch", (U32, U32, U32)), ("strings", (HI_MAX, N_MAX, HI_MAX)), ("strdec", (HI_MAX, N_MAX, HI_MAX, 0)), ("strdec", (HI_MAX, N_MAX, HI_MAX, 1)),
           ("blkhead", (HI_MAX, N_MAX)), ("blkscan", (HI_MAX, N_MAX, U32, U32)), ("blkout", (U32, U32, U32)),
           ("blkpin", (U32, N_MAX, U32, U32, 0, 0, 0)), ("blkpin", (U32, N_MAX, U32, U32, 1, N_MAX, U32)),
           ("blkapply", (N_MAX, N_MAX, U32, U32)), ("plan", (HI_MAX, NH_MAX, N_MAX, N_MAX, U32, HI_MAX, HI_MAX))]
