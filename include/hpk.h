@@ -644,6 +644,94 @@ int hpk_h2_read_frames(hpk_ctx* ctx, hpk_h2conn* const* conns, const uint8_t* by
                        uint32_t nconn, hpk_h2_out* out);
 void hpk_h2_out_free(hpk_h2_out* out);
 
+/* ---- HTTP/2 framing: the frame scan on the device ------------------------------------------
+ * hpk_scan_frames is step 1 of hpk_h2_read_frames on many connections at once, with no decoder in hand:
+ * connection c's bytes are bytes[off[c] .. off[c+1]) and its frame state conns[c]. Per connection it does, frame by
+ * frame, what the reference does: the deframer's length check (a length above max_frame_size is FrameTooLarge even
+ * before the payload has arrived, and that frame is not consumed: crates/loona/src/h2/server.rs:318-325), an
+ * incomplete frame ends the walk unconsumed and without an error, the padding of DATA and HEADERS frames goes
+ * (server.rs:356-382: PaddedFrameEmpty, PaddedFrameTooShort; PADDED on any other type is not padding), a pending
+ * block takes only CONTINUATION frames of its stream, the stream id compared before the type (read_headers,
+ * server.rs:1376-1417: :1391-1397, then :1399-1408), a CONTINUATION with no block pending is
+ * UnexpectedContinuationFrame (server.rs:1299-1303), frames other than HEADERS are skipped, and a HEADERS frame's
+ * priority block goes (server.rs:895-911: fewer than 5 octets ReadAndParse(PrioritySpec), a 31-bit dependency equal
+ * to the stream id HeadersInvalidPriority). A stream id's reserved bit is masked (Frame::parse,
+ * crates/loona-h2/src/lib.rs:397-411). A connection whose error is set on entry consumes nothing. A frame that
+ * raises an error other than FrameTooLarge is consumed.
+ * Outputs. blocks: one hpk_fblock per header block completed in this call, in connection order, then frame order
+ * (hpk_h2_read_frames' block order); connection c's are conn_blk_off[c] .. conn_blk_off[c+1]. Block b's bytes are
+ * the fragments frag[blocks[b].frag .. + blocks[b].nfrag) of the closed list, fragment g being bytes[frag_off[g] ..
+ * frag_off[g] + frag_len[g]): the closed list holds only fragments of completed blocks, in order, so the blocks tile
+ * it. A connection that enters pending has its carry window [carry_off, carry_off + carry_len) as fragment 0 of that
+ * block, even when the window is empty (and with its error set on entry: the block then stays open). The fragments
+ * of a block still pending when the walk ends (at the connection's end, or at an error) go to the open list,
+ * connection c's at conn_open_off[c] .. conn_open_off[c+1]: their bytes, in order, are what the caller must keep as
+ * the next call's carry. The three offset arrays have nconn + 1 entries and are exclusive sums. Lengths are exact:
+ * padding, the pad-length octet and the priority block are excluded; zero-length fragments are listed. After an
+ * error a connection's walk stops: its earlier completed blocks stay listed. conns[c] comes back with error,
+ * pending, pend_stream, consumed and status updated; max_frame_size and the carry window are the caller's.
+ * Capacities: blocks_cap (records), frags_cap and opens_cap (windows) may be any size; (off[nconn] - off[0]) / 9
+ * blocks and (off[nconn] - off[0]) / 9 + nconn fragments of either list always suffice. Records and windows below
+ * the capacities are written and nothing at or past them; the offset arrays and the states are complete either way.
+ * A synchronous call returns HPK_E_NOSPACE when a total passes its capacity; HPK_E_INVAL wins over HPK_E_NOSPACE.
+ * A connection whose offsets decrease or pass cap, or whose carry window passes cap while it is pending, is void: 0
+ * blocks, 0 fragments, status HPK_BAD_OFFSETS and nothing else of its state touched, the sticky flag; it voids no
+ * other connection. cap above HPK_MAX_OFFSET is HPK_E_INVAL. nconn == 0 writes the three zeros. Nothing outside
+ * [bytes, bytes + cap) is read, and of a connection nothing outside its range (the carry window is listed, not read).
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC (conns and blocks must then be 16-byte aligned: HPK_E_INVAL); or
+ * HPK_PTR_HOST, synchronous: the offsets and carry windows are checked on the host before anything is copied
+ * (HPK_E_INVAL, nothing written; the offsets must then be non-decreasing as a whole), the input is staged in one
+ * piece into grow-only scratch of the stream's slot, and exactly the written parts come back. Always the launch
+ * path: the small-call mode does not answer it.
+ * How: a count pass (one lane per connection, 256-lane workgroups: blocks, closed and open fragments), the length
+ * scan over each count array, and an emit pass (one lane per connection again, the same walk: each block record one
+ * 16-byte store, the state two). Both passes run the walk of hpk_frmscan.h, so they cannot disagree; the count pass
+ * does not write the state. Scratch per stream: 12 bytes per connection and the scan's tile sums. Cost of a long
+ * connection: one lane walks a whole connection, two dependent byte loads per frame, so a connection of many
+ * thousands of small frames takes that many load latencies whatever the rest of the call does. */
+typedef struct hpk_fconn {      /* one connection's frame state; 32 bytes, 16-byte aligned for device calls */
+    uint32_t max_frame_size;    /* in */
+    int32_t  error;             /* in/out: hpk_h2_error, sticky (never COMPRESSION_ERROR: the scan decodes nothing) */
+    uint32_t pending;           /* in/out: 1 = a HEADERS block waits for CONTINUATION */
+    uint32_t pend_stream;       /* in/out: its stream id, bit 31 = the HEADERS frame's END_STREAM */
+    uint32_t carry_off, carry_len; /* in: where in `bytes` the caller put the fragment bytes that block has so far */
+    uint32_t consumed;          /* out: bytes of whole frames consumed */
+    uint32_t status;            /* out: HPK_OK or HPK_BAD_OFFSETS */
+} hpk_fconn;
+typedef struct hpk_fblock { uint32_t conn, stream_id /* bit 31 END_STREAM */, frag, nfrag; } hpk_fblock; /* 16 bytes */
+
+int hpk_scan_frames(hpk_ctx* ctx, const uint8_t* bytes, size_t cap, const uint32_t* off, uint32_t nconn, hpk_fconn* conns,
+                    hpk_fblock* blocks, size_t blocks_cap, uint32_t* conn_blk_off,
+                    uint32_t* frag_off, uint32_t* frag_len, size_t frags_cap, uint32_t* conn_frag_off,
+                    uint32_t* open_off, uint32_t* open_len, size_t opens_cap, uint32_t* conn_open_off, int flags);
+
+/* hpk_frame_blocks concatenates the scan's closed fragments into header blocks: the ordered pack (hpk_pack_batch's
+ * kernels) of bytes[frag_off[g] .. + frag_len[g]), g < nfrags, into out_blob, then block_off[b] = the packed offset
+ * of fragment blocks[b].frag and block_off[nblocks] = the packed total: read_headers' concatenation
+ * (server.rs:1619-1638). (out_blob, block_off) are hpk_scan_blocks' inputs as they stand. Capacity, HPK_E_NOSPACE
+ * and bad fragment windows as hpk_pack_batch. A block record whose frag passes nfrags is read as nfrags, and one
+ * whose frag goes below its predecessor's as its predecessor's; either sets the sticky flag (HPK_E_INVAL from a
+ * synchronous call). Device pointers only (HPK_PTR_DEVICE, optionally HPK_ASYNC); blocks 16-byte aligned. Scratch
+ * per stream: nfrags + 1 dwords and the pack's tile sums. */
+int hpk_frame_blocks(hpk_ctx* ctx, const uint8_t* bytes, size_t cap, const uint32_t* frag_off, const uint32_t* frag_len,
+                     uint32_t nfrags, const hpk_fblock* blocks, uint32_t nblocks,
+                     uint8_t* out_blob, size_t out_cap, uint32_t* block_off, int flags);
+
+/* Where hpk_h2_read_frames does its framing (its step 1). HPK_FRAME_SCAN_HOST (the default): on the host,
+ * connection by connection. HPK_FRAME_SCAN_DEVICE (opt-in; calls without a context are not affected): the call's
+ * bytes go up once, with every pending connection's held fragment bytes behind them as its carry, and the states;
+ * hpk_scan_frames' steps and hpk_frame_blocks' steps run; the block records, block_off, the states, the open windows
+ * and the gathered block bytes come back; connections with open fragments rebuild their held bytes from those
+ * windows; then the block decode and the error pass run as on the default path. Results, conn_error, conn_consumed
+ * and every connection's state equal the default path's exactly. Nothing is written to a connection before
+ * everything is back, so a device failure on this path leaves every connection untouched. Known cost: the blocks
+ * come back to the host and go up again when a device block path is selected (hpk_ctx_set_block_scan,
+ * hpk_ctx_set_block_apply); keeping them on the device for the block scan is not done. The call's bytes and the
+ * carries together must not pass HPK_MAX_OFFSET (HPK_E_INVAL). */
+#define HPK_FRAME_SCAN_HOST 0    /* the default: the host framing */
+#define HPK_FRAME_SCAN_DEVICE 1
+int hpk_ctx_set_frame_scan(hpk_ctx* ctx, int kind);
+
 /* ---- HPACK header blocks: encode (the response path) ----------------------
  * hpk_henc mirrors hpack::Encoder (crates/loona-hpack/src/encoder.rs:172-335): one per
  * connection, holding the dynamic table, with the reference's single strategy (a header found
@@ -686,7 +774,9 @@ void hpk_henc_out_free(hpk_henc_out* out);
 /* A failed hpk_henc_encode_blocks (any negative return) leaves every encoder's dynamic table as it
  * was before the call, as a failed hpk_henc_encode does; the blocks are then not sent at all.
  * Testing only: the calling thread's next n Huffman batches inside hpk_henc_encode_blocks fail
- * with HPK_E_DEVICE (n = 0 clears it), so that guarantee can be checked without a device fault. */
+ * with HPK_E_DEVICE (n = 0 clears it), so that guarantee can be checked without a device fault. The
+ * device frame scan of hpk_h2_read_frames (HPK_FRAME_SCAN_DEVICE) counts as one such batch: it fails
+ * the same way before it touches the device, and every connection stays as it was. */
 void hpk_test_fail_batches(int n);
 
 /* ---- HPACK header blocks: the encoder's table half on the device ---------------------------
@@ -849,6 +939,9 @@ int hpk_test_small_set_request(hpk_ctx* ctx, uint32_t v);
 /* Testing only: the block scan's geometry (hpk_scan_blocks): the blocks a workgroup of either pass walks, one
  * per lane. The tests place their block counts relative to it. */
 int hpk_test_blkscan_geometry(uint32_t* wg_blocks);
+/* Testing only: the frame scan's geometry (hpk_scan_frames): the connections a workgroup of either pass walks,
+ * one per lane. The tests place their connection counts relative to it. */
+int hpk_test_frmscan_geometry(uint32_t* wg_conns);
 
 /* Library/kernel identification (for logs and the bench JSON). */
 const char* hpk_version(void);

@@ -41,6 +41,10 @@ HPK_MAX_OFFSET = 0xFFFFFFDF  # offsets of one shard stay at or below this (hpk.h
 HPK_BLOCK_SCAN_HOST = 0
 HPK_BLOCK_SCAN_DEVICE = 1
 
+# hpk_ctx_set_frame_scan (hpk.h)
+HPK_FRAME_SCAN_HOST = 0
+HPK_FRAME_SCAN_DEVICE = 1
+
 # hpk_ctx_set_block_apply (hpk.h)
 HPK_BLOCK_APPLY_HOST = 0
 HPK_BLOCK_APPLY_DEVICE = 1
@@ -121,6 +125,9 @@ EXPORTS = (
     "hpk_h2_error_code",
     "hpk_h2_read_frames",
     "hpk_h2_out_free",
+    "hpk_scan_frames",
+    "hpk_frame_blocks",
+    "hpk_ctx_set_frame_scan",
     "hpk_henc_create",
     "hpk_henc_destroy",
     "hpk_henc_set_max_table_size",
@@ -140,6 +147,7 @@ EXPORTS = (
     "hpk_test_persist_geometry",
     "hpk_test_small_set_request",
     "hpk_test_blkscan_geometry",
+    "hpk_test_frmscan_geometry",
     "hpk_ctx_set_decode_kernel",
     "hpk_ctx_set_small_mode",
     "hpk_version",
@@ -250,6 +258,20 @@ def lib() -> ctypes.CDLL:
             L.hpk_scan_blocks.restype = ctypes.c_int
             L.hpk_ctx_set_block_scan.argtypes = [ctypes.c_void_p, ctypes.c_int]
             L.hpk_ctx_set_block_scan.restype = ctypes.c_int
+        if hasattr(L, "hpk_scan_frames"):  # (likewise: no frame scan)
+            L.hpk_scan_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
+            L.hpk_scan_frames.restype = ctypes.c_int
+            L.hpk_frame_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.c_void_p, ctypes.c_int]
+            L.hpk_frame_blocks.restype = ctypes.c_int
+            L.hpk_ctx_set_frame_scan.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.hpk_ctx_set_frame_scan.restype = ctypes.c_int
+            L.hpk_test_frmscan_geometry.argtypes = [c_u32p]
+            L.hpk_test_frmscan_geometry.restype = ctypes.c_int
         if hasattr(L, "hpk_apply_blocks"):  # (likewise: no block apply)
             L.hpk_apply_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,

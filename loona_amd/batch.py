@@ -33,6 +33,10 @@ HREP_DTYPE = np.dtype([("index", "<u4"), ("kind", "u1"), ("prefix_len", "u1"), (
 # hpk_field (hpk.h): one 16-byte record of scan_blocks
 FIELD_DTYPE = np.dtype([("index", "<u4"), ("str", "<u4"), ("kind", "u1"), ("nstr", "u1"), ("err", "u1"),
                         ("err_stage", "u1"), ("at", "<u4")])
+# hpk_fconn and hpk_fblock (hpk.h): scan_frames' 32-byte connection states and 16-byte block records
+FCONN_DTYPE = np.dtype([("max_frame_size", "<u4"), ("error", "<i4"), ("pending", "<u4"), ("pend_stream", "<u4"),
+                        ("carry_off", "<u4"), ("carry_len", "<u4"), ("consumed", "<u4"), ("status", "<u4")])
+FBLOCK_DTYPE = np.dtype([("conn", "<u4"), ("stream_id", "<u4"), ("frag", "<u4"), ("nfrag", "<u4")])
 
 
 def pack(literals):
@@ -707,6 +711,141 @@ class HuffmanCodec:
         self._scan_blocks_call(blocks, block_off, fields, field_off, str_off, str_end, str_blk_off, status, False, True)
         nf, ns = int(field_off[n]), int(str_blk_off[n])
         return fields[: 16 * nf].view(FIELD_DTYPE), field_off, str_off[:ns], str_end[:ns], str_blk_off, status[:n]
+
+    FRAME_SCANS = {"host": _lib.HPK_FRAME_SCAN_HOST, "device": _lib.HPK_FRAME_SCAN_DEVICE}
+
+    def set_frame_scan(self, kind: str):
+        """'host' (the default) or 'device' (hpk_ctx_set_frame_scan): where h2.read_frames does its framing with
+        this codec. The same results and connection states; 'device' uploads the call's bytes with the pending
+        connections' held fragments behind them and runs scan_frames' and frame_blocks' kernels before the blocks
+        are decoded."""
+        if kind not in self.FRAME_SCANS:
+            raise ValueError(f"frame scan {kind!r} not in {tuple(self.FRAME_SCANS)}")
+        _lib.check(self._L.hpk_ctx_set_frame_scan(self._h, self.FRAME_SCANS[kind]), "hpk_ctx_set_frame_scan")
+
+    def _scan_frames_call(self, data, off, conns, blocks, conn_blk_off, frag_off, frag_len, conn_frag_off, open_off, open_len,
+                          conn_open_off, device, sync):
+        dev = self.device if device else None
+        n = int(off.shape[0]) - 1
+        if n < 0:
+            raise ValueError("off needs nconn+1 >= 1 entries")
+        pb, cap = _arg(data, "bytes", ("uint8",), 0, dev)
+        po, _ = _arg(off, "off", _OFF_DTYPES, n + 1, dev)
+        pc, _ = _arg(conns, "conns", ("uint8",), 32 * n, dev)
+        pk, kbytes = _arg(blocks, "blocks", ("uint8",), 0, dev)
+        pcb, _ = _arg(conn_blk_off, "conn_blk_off", _OFF_DTYPES, n + 1, dev)
+        pfo, fobytes = _arg(frag_off, "frag_off", _OFF_DTYPES, 0, dev)
+        pfl, flbytes = _arg(frag_len, "frag_len", _OFF_DTYPES, 0, dev)
+        pcf, _ = _arg(conn_frag_off, "conn_frag_off", _OFF_DTYPES, n + 1, dev)
+        poo, oobytes = _arg(open_off, "open_off", _OFF_DTYPES, 0, dev)
+        pol, olbytes = _arg(open_len, "open_len", _OFF_DTYPES, 0, dev)
+        pco, _ = _arg(conn_open_off, "conn_open_off", _OFF_DTYPES, n + 1, dev)
+        if device:
+            self._follow()
+            flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        else:
+            flags = _lib.HPK_PTR_HOST
+        rc = self._L.hpk_scan_frames(self._h, pb, cap, po, ctypes.c_uint32(n), pc, pk, kbytes // 16, pcb, pfo, pfl,
+                                     min(fobytes, flbytes) // 4, pcf, poo, pol, min(oobytes, olbytes) // 4, pco, flags)
+        _lib.check(rc, "hpk_scan_frames")
+
+    def scan_frames(self, data, off, conns, blocks=None, conn_blk_off=None, frag_off=None, frag_len=None, conn_frag_off=None,
+                    open_off=None, open_len=None, conn_open_off=None, sync=False):
+        """hpk_scan_frames: torch cuda tensors -> (blocks, conn_blk_off, frag_off, frag_len, conn_frag_off, open_off,
+        open_len, conn_open_off); conns is updated in place. Connection c's bytes are data[off[c] : off[c + 1]] and
+        its frame state the 32-byte hpk_fconn record conns[32 c : 32 c + 32] (a uint8 tensor: view it with
+        FCONN_DTYPE on the host). blocks is a uint8 tensor of 16-byte hpk_fblock records (FBLOCK_DTYPE), one per
+        header block completed in the call, connection c's from conn_blk_off[c]: block b's bytes are the closed
+        fragments frag .. frag + nfrag, fragment g being data[frag_off[g] : frag_off[g] + frag_len[g]]. The open list
+        holds the fragments of blocks still pending, connection c's from conn_open_off[c]: the next call's carry.
+        The capacities are the tensors' sizes; what is allocated here holds (off[-1] - off[0]) // 9 blocks and that
+        plus nconn fragments of either list, which always suffices (it reads off[0] and off[-1] back for that). With
+        sync=True a list that does not fit raises (HPK_E_NOSPACE)."""
+        import torch
+
+        n = int(off.shape[0]) - 1
+        dev = data.device
+        if blocks is None or frag_off is None or frag_len is None or open_off is None or open_len is None:
+            span = ((int(off[n].item()) & 0xFFFFFFFF) - (int(off[0].item()) & 0xFFFFFFFF)) if n > 0 else 0
+            mb = max(span, 0) // 9
+            mf = mb + max(n, 0)
+        if blocks is None:
+            blocks = torch.empty(16 * max(mb, 1), dtype=torch.uint8, device=dev)[: 16 * mb]
+        if frag_off is None:
+            frag_off = torch.empty(max(mf, 1), dtype=torch.int32, device=dev)[:mf]
+        if frag_len is None:
+            frag_len = torch.empty(max(mf, 1), dtype=torch.int32, device=dev)[:mf]
+        if open_off is None:
+            open_off = torch.empty(max(mf, 1), dtype=torch.int32, device=dev)[:mf]
+        if open_len is None:
+            open_len = torch.empty(max(mf, 1), dtype=torch.int32, device=dev)[:mf]
+        if conn_blk_off is None:
+            conn_blk_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if conn_frag_off is None:
+            conn_frag_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if conn_open_off is None:
+            conn_open_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        self._scan_frames_call(data, off, conns, blocks, conn_blk_off, frag_off, frag_len, conn_frag_off, open_off, open_len,
+                               conn_open_off, True, sync)
+        return blocks, conn_blk_off, frag_off, frag_len, conn_frag_off, open_off, open_len, conn_open_off
+
+    def scan_frames_host(self, data, off, conns, blocks_cap=None, frags_cap=None, opens_cap=None):
+        """hpk_scan_frames with host pointers: numpy in -> (conns, blocks, conn_blk_off, frag_off, frag_len,
+        conn_frag_off, open_off, open_len, conn_open_off), staged through the context and synchronous. conns is an
+        FCONN_DTYPE record array (a copy comes back updated), blocks an FBLOCK_DTYPE one. The offsets and the carry
+        windows are checked before anything is copied. The capacities default to what always suffices; the lists come
+        back cut to their totals when they fit, and the call raises (HPK_E_NOSPACE) when one does not."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=U32)
+        conns = np.array(conns, dtype=FCONN_DTYPE, copy=True)
+        n = len(off) - 1
+        if len(conns) != n:
+            raise ValueError(f"conns: {len(conns)} records for {n} connections")
+        span = int(off[n]) - int(off[0]) if n > 0 else 0
+        mb = max(span, 0) // 9
+        bcap = int(mb if blocks_cap is None else blocks_cap)
+        fcap = int(mb + n if frags_cap is None else frags_cap)
+        ocap = int(mb + n if opens_cap is None else opens_cap)
+        blocks = np.zeros(16 * max(bcap, 1), dtype=np.uint8)[: 16 * bcap]
+        fo, fl = np.zeros(max(fcap, 1), dtype=U32)[:fcap], np.zeros(max(fcap, 1), dtype=U32)[:fcap]
+        oo, ol = np.zeros(max(ocap, 1), dtype=U32)[:ocap], np.zeros(max(ocap, 1), dtype=U32)[:ocap]
+        cb, cf, co = np.zeros(n + 1, dtype=U32), np.zeros(n + 1, dtype=U32), np.zeros(n + 1, dtype=U32)
+        if data.size == 0:
+            data = np.zeros(1, dtype=np.uint8)[:0]
+        raw = conns.view(np.uint8).reshape(-1) if n else np.zeros(1, dtype=np.uint8)[:0]
+        self._scan_frames_call(data, off, raw, blocks, cb, fo, fl, cf, oo, ol, co, False, True)
+        nb, nf, no = int(cb[n]), int(cf[n]), int(co[n])
+        return conns, blocks[: 16 * nb].view(FBLOCK_DTYPE), cb, fo[:nf], fl[:nf], cf, oo[:no], ol[:no], co
+
+    def frame_blocks(self, data, frag_off, frag_len, blocks, nblocks=None, out_blob=None, block_off=None, sync=False):
+        """hpk_frame_blocks: torch cuda tensors -> (out_blob, block_off): scan_frames' closed fragments (all of
+        frag_off / frag_len as given: cut them to the total) laid end to end in out_blob, block b's bytes being
+        out_blob[block_off[b] : block_off[b + 1]]: scan_blocks' inputs as they stand. blocks is scan_frames' uint8
+        tensor of hpk_fblock records, nblocks of them (default: all of the tensor). out_blob=None allocates data's
+        size (fragments of a scan never sum to more), cut to the total when sync=True; capacity rules as pack."""
+        import torch
+
+        nf = int(frag_len.shape[0])
+        nb = int(blocks.numel()) // 16 if nblocks is None else int(nblocks)
+        dev = self.device
+        pd, cap = _arg(data, "bytes", ("uint8",), 0, dev)
+        pfo, _ = _arg(frag_off, "frag_off", _OFF_DTYPES, nf, dev)
+        pfl, _ = _arg(frag_len, "frag_len", _OFF_DTYPES, nf, dev)
+        pk, _ = _arg(blocks, "blocks", ("uint8",), 16 * nb, dev)
+        own = out_blob is None
+        if own:
+            out_blob = torch.empty(max(int(data.numel()), 1), dtype=torch.uint8, device=data.device)
+        if block_off is None:
+            block_off = torch.empty(nb + 1, dtype=torch.int32, device=data.device)
+        po, out_cap = _arg(out_blob, "out_blob", ("uint8",), 0, dev)
+        pbo, _ = _arg(block_off, "block_off", _OFF_DTYPES, nb + 1, dev)
+        self._follow()
+        flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        rc = self._L.hpk_frame_blocks(self._h, pd, cap, pfo, pfl, ctypes.c_uint32(nf), pk, ctypes.c_uint32(nb), po, out_cap, pbo, flags)
+        _lib.check(rc, "hpk_frame_blocks")
+        if own and sync:
+            out_blob = out_blob[: int(block_off[nb].item()) & 0xFFFFFFFF]
+        return out_blob, block_off
 
     BLOCK_APPLIES = {"host": _lib.HPK_BLOCK_APPLY_HOST, "device": _lib.HPK_BLOCK_APPLY_DEVICE}
 

@@ -72,12 +72,16 @@ struct hpk_slot {
     DevBuf bp_hash;
     // the block encoder's device-plan path: the arena, the lists, the tables, the items and the coded bytes
     DevBuf bp_buf;
+    // the frame scan (hpk_scan_frames): the count pass's three arrays; the staged input, states and arrays of its host
+    // form and of hpk_h2_read_frames' device path; and that path's lists and gathered blocks, sized once the totals
+    // are known (hpk_frame_blocks keeps its nfrags + 1 packed offsets there)
+    DevBuf fs_meta, fs_stage, fs_out;
     // every buffer above: the one list of them (hpk_ctx_destroy frees through it)
-    static constexpr size_t kBufs = 17;
+    static constexpr size_t kBufs = 20;
     template <class F>
     void each_buf(F f) {
         for (DevBuf* b : {&long_list, &cp_bound, &cp_tmp, &cp_cursor, &pk_scratch, &pk_bound, &pk_tmp, &str_stage, &sd_meta, &sd_hblob,
-                          &sd_stage, &bs_meta, &bs_stage, &bs_out, &ba_buf, &bp_hash, &bp_buf})
+                          &sd_stage, &bs_meta, &bs_stage, &bs_out, &ba_buf, &bp_hash, &bp_buf, &fs_meta, &fs_stage, &fs_out})
             f(*b);
     }
 };
@@ -91,6 +95,7 @@ struct hpk_ctx {
     int block_scan = HPK_BLOCK_SCAN_HOST;  // hpk_ctx_set_block_scan
     int block_apply = HPK_BLOCK_APPLY_HOST;  // hpk_ctx_set_block_apply
     int block_plan = HPK_BLOCK_PLAN_HOST;  // hpk_ctx_set_block_plan
+    int frame_scan = HPK_FRAME_SCAN_HOST;  // hpk_ctx_set_frame_scan
     uint64_t plan_calls = 0;  // hpk_henc_encode_blocks calls the device-plan path answered (hpk_test_plan_calls)
     hpk_header* d_static = nullptr;  // hpk_static_table's 61 records, uploaded by the first hpk_apply_blocks
     hipStream_t own = nullptr;
@@ -266,5 +271,21 @@ int hpk_launch_blkplan(hpk_ctx* c, uint8_t* arena, uint32_t arena_cap, uint32_t 
 
 // boff[b] = out_off[3 * hdr_off[b]] for b <= nblocks: where block b's bytes begin in the strings call's output.
 int hpk_launch_blkplan_boff(hpk_ctx* c, const uint32_t* out_off, const uint32_t* hdr_off, uint32_t nblocks, uint32_t* boff);
+
+// The frame scan's passes (hpk_frmscan.hip), on the ctx stream, around hpk_len_scan and hpk_pack_launch. The count pass:
+// connection c = blob[off[c] .. off[c+1]) with state conns[c] gives nblk[c], nclosed[c] and nopen[c], all 0 with the
+// sticky flag for a void connection; it does not write the states. The emit pass: the same walk, the block records to
+// blocks from conn_blk_off[c], the closed windows to frag_off / frag_len from conn_frag_off[c], the open ones to
+// open_off / open_len from conn_open_off[c], each only below its capacity, then the state; conns and blocks are
+// 16-byte aligned. hpk_launch_frmboff: block_off[b] = dst_off[blocks[b].frag] (clamped, hpk_frame_blocks) for b <
+// nblocks and block_off[nblocks] = dst_off[nfrags].
+int hpk_launch_frmcount(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint32_t* off, uint32_t nconn, const hpk_fconn* conns,
+                        uint32_t* nblk, uint32_t* nclosed, uint32_t* nopen);
+int hpk_launch_frmemit(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint32_t* off, uint32_t nconn, hpk_fconn* conns,
+                       const uint32_t* conn_blk_off, const uint32_t* conn_frag_off, const uint32_t* conn_open_off, hpk_fblock* blocks,
+                       uint32_t blocks_cap, uint32_t* frag_off, uint32_t* frag_len, uint32_t frags_cap, uint32_t* open_off,
+                       uint32_t* open_len, uint32_t opens_cap);
+int hpk_launch_frmboff(hpk_ctx* c, const uint32_t* dst_off, uint32_t nfrags, const hpk_fblock* blocks, uint32_t nblocks,
+                       uint32_t* block_off);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

@@ -15,10 +15,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
 #include <new>
 #include <vector>
 
 #include "../../include/hpk.h"
+#include "hpk_internal.h"
 
 namespace {
 
@@ -80,6 +83,80 @@ extern "C" int hpk_h2_error_code(int err) {  // H2ConnectionError::as_known_erro
     }
 }
 
+// The device half's frame scan (hpk_internal.h: hpk_frames_device), installed by hpk_ctx_create; null where only
+// the host half is linked. The host units name no symbol of the device half for it.
+static std::atomic<hpk_frames_device_fn> g_frames_device{nullptr};
+void hpk_h2_set_frames_device(hpk_frames_device_fn fn) { g_frames_device.store(fn, std::memory_order_relaxed); }
+
+// Step 1 of hpk_h2_read_frames through the device (HPK_FRAME_SCAN_DEVICE): the states and the held fragment bytes
+// of the pending connections are laid out as hpk_scan_frames takes them, the device function answers, and only then
+// are the connections written: their states from the scan's, their held bytes from the open windows (a window at
+// or past off[nconn] lies in the bytes held before). -> HPK_E_OK, HPK_FRAMES_NOT_SELECTED with nothing done (the
+// function, asked with no job, says whether the context selects it), or a
+// negative code with no connection touched. A connection listed twice in one call is HPK_E_INVAL on this path: the
+// lanes walk the connections independently.
+static int frames_on_device(hpk_frames_device_fn fn, hpk_ctx* ctx, hpk_h2conn* const* conns, const uint8_t* bytes,
+                            const uint32_t* off, uint32_t nconn, hpk_h2_out* out, std::vector<uint8_t>& blk,
+                            std::vector<uint32_t>& boff, std::vector<hpk_hdec*>& decs, std::vector<hpk_h2_block>& meta,
+                            std::vector<int32_t>& frame_err) {
+    if (fn(ctx, nullptr) != HPK_E_OK) return HPK_FRAMES_NOT_SELECTED;
+    {
+        std::vector<const hpk_h2conn*> seen(conns, conns + nconn);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return HPK_E_INVAL;
+    }
+    const uint32_t hi = off[nconn];
+    std::vector<hpk_fconn> st(nconn);
+    std::vector<uint8_t> carry;
+    std::vector<uint32_t> coo((size_t)nconn + 1, 0);
+    for (uint32_t c = 0; c < nconn; ++c) {
+        const hpk_h2conn* k = conns[c];
+        st[c] = hpk_fconn{k->max_frame_size, k->error, k->pending ? 1u : 0u, k->pend_stream | (k->pend_end_stream << 31), 0u, 0u, 0u, 0u};
+        if (!k->pending) continue;
+        if ((uint64_t)hi + carry.size() + k->frag.size() > HPK_MAX_OFFSET) return HPK_E_INVAL;
+        st[c].carry_off = hi + (uint32_t)carry.size();
+        st[c].carry_len = (uint32_t)k->frag.size();
+        carry.insert(carry.end(), k->frag.begin(), k->frag.end());
+    }
+    hpk_frmjob job{};
+    job.bytes = bytes;
+    job.off = off;
+    job.nconn = nconn;
+    job.conns = st.data();
+    job.carry = carry.data();
+    job.ncarry = (uint32_t)carry.size();
+    job.conn_open_off = coo.data();
+    if (const int rc = fn(ctx, &job)) return rc;  // (failed: nothing was written)
+    // everything is back: the new held bytes first (they read the old ones), then the connections
+    std::vector<std::vector<uint8_t>> held(nconn);
+    for (uint32_t c = 0; c < nconn; ++c)
+        for (uint32_t w = coo[c]; w < coo[c + 1]; ++w) {
+            const uint32_t a = job.open_off[w], n = job.open_len[w];
+            const uint8_t* p = a >= hi ? carry.data() + (a - hi) : bytes + a;
+            held[c].insert(held[c].end(), p, p + n);
+        }
+    for (uint32_t c = 0; c < nconn; ++c) {
+        hpk_h2conn* k = conns[c];
+        k->error = st[c].error;
+        k->pending = st[c].pending != 0;
+        k->pend_stream = st[c].pend_stream & 0x7FFFFFFFu;
+        k->pend_end_stream = st[c].pend_stream >> 31;
+        k->frag.swap(held[c]);
+        out->conn_consumed[c] = st[c].consumed;
+        frame_err[c] = st[c].error;
+    }
+    const uint32_t nb = job.nblocks;
+    blk.assign(job.blk, job.blk + job.block_off[nb]);
+    boff.assign(job.block_off, job.block_off + nb + 1);
+    for (uint32_t b = 0; b < nb; ++b) {
+        const hpk_fblock& f = job.blocks[b];
+        decs.push_back(conns[f.conn]->dec);
+        meta.push_back(hpk_h2_block{f.conn, f.stream_id & 0x7FFFFFFFu, f.stream_id >> 31, 0u});
+    }
+    free(job.blocks), free(job.block_off), free(job.blk), free(job.open_off), free(job.open_len);
+    return HPK_E_OK;
+}
+
 extern "C" int hpk_h2_read_frames(hpk_ctx* ctx, hpk_h2conn* const* conns, const uint8_t* bytes, const uint32_t* off,
                                   uint32_t nconn, hpk_h2_out* out) {
     if (!conns || !off || !out || (nconn && off[nconn] > off[0] && !bytes)) return HPK_E_INVAL;
@@ -106,7 +183,16 @@ extern "C" int hpk_h2_read_frames(hpk_ctx* ctx, hpk_h2conn* const* conns, const 
         meta.push_back(hpk_h2_block{c, sid, end_stream, 0u});
     };
     std::vector<int32_t> frame_err(nconn, HPK_H2_OK);  // framing errors found this call
-    for (uint32_t c = 0; c < nconn; ++c) {
+    // with a context on HPK_FRAME_SCAN_DEVICE the device does this step (include/hpk.h); else the loop below
+    int on_device = HPK_FRAMES_NOT_SELECTED;
+    if (const hpk_frames_device_fn fn = ctx ? g_frames_device.load(std::memory_order_relaxed) : nullptr) {
+        on_device = frames_on_device(fn, ctx, conns, bytes, off, nconn, out, blk, boff, decs, meta, frame_err);
+        if (on_device < 0) {
+            hpk_h2_out_free(out);
+            return on_device;
+        }
+    }
+    for (uint32_t c = 0; on_device == HPK_FRAMES_NOT_SELECTED && c < nconn; ++c) {
         hpk_h2conn* k = conns[c];
         size_t pos = off[c];
         const size_t end = off[c + 1];

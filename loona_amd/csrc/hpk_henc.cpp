@@ -186,13 +186,15 @@ extern "C" int hpk_henc_encode(hpk_henc* e, const uint8_t* fields, const uint32_
 static thread_local int t_fail_batches = 0;
 extern "C" void hpk_test_fail_batches(int n) { t_fail_batches = n > 0 ? n : 0; }
 
-namespace {
-
-int injected_failure() {  // -> 0, or the error of a batch the hook makes fail
+int hpk_test_take_failure() {  // -> 0, or the error of a batch the hook makes fail (hpk_internal.h)
     if (t_fail_batches <= 0) return 0;
     --t_fail_batches;
     return hpk_set_err_msg("injected batch failure (hpk_test_fail_batches)", HPK_E_DEVICE);
 }
+
+namespace {
+
+int injected_failure() { return hpk_test_take_failure(); }
 
 // What the device-plan path sends up: the arena (the static text, every encoder's live entries' bytes, the fields), and over it the
 // tables, the fields' offsets from the first field's and the blocks' header offsets from the first block's.

@@ -1,4 +1,4 @@
-// hpk_internal.h — declarations shared between the host units of libhpk (hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp) and its
+// hpk_internal.h — declarations shared between the host units of libhpk (hpk_cpu.cpp, hpk_hdec.cpp, hpk_henc.cpp, hpk_h2.cpp) and its
 // device half (hpk_ctx.hip and the hpk_calls_*.hip call layer). Not part of the C ABI.
 #pragma once
 #include <stddef.h>
@@ -91,3 +91,37 @@ void hpk_ctx_plan_answered(hpk_ctx* c);    // the caller has committed such a ca
 int hpk_ctx_block_plan(const hpk_ctx* c);  // hpk_ctx_set_block_plan's value (HPK_BLOCK_PLAN_HOST for no context)
 int hpk_ctx_block_scan(const hpk_ctx* c);  // hpk_ctx_set_block_scan's value (HPK_BLOCK_SCAN_HOST for no context)
 int hpk_ctx_block_apply(const hpk_ctx* c);  // hpk_ctx_set_block_apply's value (HPK_BLOCK_APPLY_HOST for no context)
+
+// hpk_h2_read_frames' device frame scan (hpk_calls_frames.hip: hpk_frames_device; used by hpk_h2.cpp,
+// HPK_FRAME_SCAN_DEVICE). hpk_h2.cpp reaches it through a pointer that it defines itself and hpk_ctx_create installs
+// (hpk_h2_set_frames_device), so the host units take no symbol of the device half for it: the pointer is null where
+// only the host half is linked. The installed function returns HPK_FRAMES_NOT_SELECTED for a context on
+// HPK_FRAME_SCAN_HOST (a null job asks just that: HPK_E_OK says selected), and else HPK_E_OK with everything on the
+// host, or a negative code with nothing written.
+struct hpk_frmjob {
+    // in (host memory): the call's bytes and offsets as hpk_h2_read_frames got them; the states as hpk_scan_frames
+    // takes them, a pending connection's carry_off counted from off[nconn]: into `carry`, the held fragment bytes of
+    // the pending connections end to end (ncarry bytes)
+    const uint8_t* bytes;
+    const uint32_t* off;
+    uint32_t nconn;
+    hpk_fconn* conns;  // in / out
+    const uint8_t* carry;
+    uint32_t ncarry;
+    // out, the caller's arrays: conn_open_off (nconn + 1); the rest from malloc, the caller's to free (null when the
+    // call fails): the block records, block_off (nblocks + 1), the blocks' bytes (block_off[nblocks] of them) and the
+    // open windows (conn_open_off[nconn] of them; an offset at or past off[nconn] lies in `carry`)
+    uint32_t* conn_open_off;
+    uint32_t nblocks;
+    hpk_fblock* blocks;
+    uint32_t* block_off;
+    uint8_t* blk;
+    uint32_t* open_off;
+    uint32_t* open_len;
+};
+enum { HPK_FRAMES_NOT_SELECTED = 1 };
+typedef int (*hpk_frames_device_fn)(hpk_ctx* c, hpk_frmjob* job);
+void hpk_h2_set_frames_device(hpk_frames_device_fn fn);  // hpk_h2.cpp
+int hpk_frames_device(hpk_ctx* c, hpk_frmjob* job);      // hpk_calls_frames.hip
+// hpk_henc.cpp: hpk_test_fail_batches' count, taken by one: 0, or the injected failure's code with its message set
+int hpk_test_take_failure();

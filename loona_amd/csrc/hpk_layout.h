@@ -243,3 +243,67 @@ static inline hpk_lay_plan hpk_layout_plan(size_t arena_cap, size_t nh, size_t n
     l.bytes = k.end + out_cap + 16;
     return l;
 }
+
+// fs_stage. The head, all that hpk_h2_read_frames' device path keeps there: bytes (the carries behind the call's) |
+// off | conns | conn_blk_off | conn_frag_off | conn_open_off. The frame scan's host form has its lists behind it:
+// blocks | frag_off | frag_len | open_off | open_len.
+struct hpk_lay_frmhead {
+    hpk_at<uint8_t> in;
+    hpk_at<uint32_t> off, cboff, cfoff, cooff;
+    hpk_at<hpk_fconn> conns;
+    size_t bytes;
+};
+struct hpk_lay_frmscan : hpk_lay_frmhead {
+    hpk_at<hpk_fblock> blocks;
+    hpk_at<uint32_t> fo, fl, oo, ol;
+};
+static inline void hpk_layout_frmhead(hpk_carve& k, hpk_lay_frmhead& l, size_t hi, size_t nconn) {
+    l.in = k.blob(hi);
+    l.off = k.take<uint32_t>(nconn + 1);
+    l.conns = k.take<hpk_fconn>(nconn);
+    l.cboff = k.take<uint32_t>(nconn + 1);
+    l.cfoff = k.take<uint32_t>(nconn + 1);
+    l.cooff = k.take<uint32_t>(nconn + 1);
+    l.bytes = k.end + 16;
+}
+static inline hpk_lay_frmhead hpk_layout_frmhead(size_t hi, size_t nconn) {
+    hpk_carve k;
+    hpk_lay_frmhead l;
+    hpk_layout_frmhead(k, l, hi, nconn);
+    return l;
+}
+static inline hpk_lay_frmscan hpk_layout_frmscan(size_t hi, size_t nconn, size_t bcap, size_t fcap, size_t ocap) {
+    hpk_carve k;
+    hpk_lay_frmscan l;
+    hpk_layout_frmhead(k, l, hi, nconn);
+    l.blocks = k.take<hpk_fblock>(bcap);
+    l.fo = k.take<uint32_t>(fcap);
+    l.fl = k.take<uint32_t>(fcap);
+    l.oo = k.take<uint32_t>(ocap);
+    l.ol = k.take<uint32_t>(ocap);
+    l.bytes = k.end + 16;
+    return l;
+}
+
+// fs_out, the device path's lists and gathered blocks: blocks | frag_off | frag_len | open_off | open_len | the
+// fragments' packed offsets | block_off | out
+struct hpk_lay_frmout {
+    hpk_at<hpk_fblock> blocks;
+    hpk_at<uint32_t> fo, fl, oo, ol, doff, boff;
+    hpk_at<uint8_t> out;
+    size_t bytes;
+};
+static inline hpk_lay_frmout hpk_layout_frmout(size_t nb, size_t nf, size_t no, size_t out_cap) {
+    hpk_carve k;
+    hpk_lay_frmout l;
+    l.blocks = k.take<hpk_fblock>(nb);
+    l.fo = k.take<uint32_t>(nf);
+    l.fl = k.take<uint32_t>(nf);
+    l.oo = k.take<uint32_t>(no);
+    l.ol = k.take<uint32_t>(no);
+    l.doff = k.take<uint32_t>(nf + 1);
+    l.boff = k.take<uint32_t>(nb + 1);
+    l.out = {k.end};
+    l.bytes = k.end + out_cap + 16;
+    return l;
+}
