@@ -732,6 +732,54 @@ int hpk_frame_blocks(hpk_ctx* ctx, const uint8_t* bytes, size_t cap, const uint3
 #define HPK_FRAME_SCAN_DEVICE 1
 int hpk_ctx_set_frame_scan(hpk_ctx* ctx, int kind);
 
+/* ---- HTTP/2 framing: the frame write on the device ------------------------------------------
+ * hpk_write_frames turns header blocks into what goes on the wire, the mirror of hpk_scan_frames + hpk_frame_blocks:
+ * block b is blocks[block_off[b] .. block_off[b+1]) with length L, and M = max_frame[b] is the peer's
+ * SETTINGS_MAX_FRAME_SIZE for that block's connection. Its wire form is the reference's loop in send_data_maybe
+ * (crates/loona/src/h2/server.rs:470-508): while the piece left is strictly longer than M, a frame of M octets with
+ * flags 0, the first such frame HEADERS (0x1), the later ones CONTINUATION (0x9); then the last piece, of 1..M octets
+ * (or of 0 when L = 0: a HEADERS frame of length 0), with END_HEADERS (0x4). So there are max(1, ceil(L / M)) frames,
+ * L = k M gives k frames with no empty CONTINUATION behind them, and the wire length is L + 9 frames (computed in 64
+ * bits). Each frame's header is Frame::write_into's (crates/loona-h2/src/lib.rs:413-422): the 24-bit big-endian
+ * length, the type, the flags, and the 31-bit stream id big-endian with the reserved bit 0. stream_id[b]'s bit 31
+ * puts END_STREAM (0x1) into the HEADERS frame's flags, never into a CONTINUATION's: hpk_fblock's convention, so a
+ * scanned block can be written back as it stands (the reference sets END_STREAM on DATA; here it is the caller's).
+ * Outputs. wire_off (nblocks + 1 entries) is the exclusive sum of the wire lengths; block b's frames are
+ * out_blob[wire_off[b] .. wire_off[b+1]) with no gap; status[b] is HPK_OK or HPK_BAD_OFFSETS. nblocks == 0 writes
+ * wire_off[0] = 0.
+ * out_cap may be any size: the octets below min(wire_off[n], out_cap) are written, nothing at or past that point nor
+ * outside [out_blob, out_blob + out_cap), and wire_off and status are complete either way. If wire_off[n] > out_cap
+ * a synchronous call returns HPK_E_NOSPACE; after HPK_ASYNC the caller compares. HPK_E_INVAL wins over it.
+ * Void blocks (device pointers): a block whose offsets decrease or pass cap, or whose max_frame is 0 (the reference's
+ * loop never ends) or above 0xFFFFFF (the length field has 24 bits), contributes 0 octets, gets HPK_BAD_OFFSETS and
+ * sets the sticky flag (HPK_E_INVAL from a synchronous call); it voids no other block. A wire total past
+ * HPK_MAX_OFFSET voids every block, zeroes every wire_off and writes no octet. cap above HPK_MAX_OFFSET is
+ * HPK_E_INVAL. Nothing outside [blocks, blocks + cap) is read beyond the aligned dwords that hold it.
+ * Pointers: HPK_PTR_DEVICE, optionally HPK_ASYNC; or HPK_PTR_HOST, synchronous: the offsets (non-decreasing as a
+ * whole, within cap) and the frame sizes are checked on the host before anything is copied (HPK_E_INVAL, nothing
+ * written), the input is staged in one piece into grow-only scratch of the stream's slot, and exactly
+ * min(wire_off[n], out_cap) octets come back. A total past HPK_MAX_OFFSET is then HPK_E_INVAL with every wire_off 0
+ * and every status HPK_BAD_OFFSETS. Always the launch path: the small-call mode does not answer it.
+ * How: the length scan over the blocks' wire lengths (64-bit tile sums), an elementwise status pass, and hpk_frmwrite,
+ * destination-centric like the ordered pack: a thread makes one aligned 16-byte chunk of the wire; position p of a
+ * block lies in frame p / (M + 9) at r = p % (M + 9), a header octet made in registers when r < 9, else source octet
+ * block_off[b] + f M + r - 9. Scratch per stream: the scan's tile sums.
+ * hpk_write_frames_cpu is the same on the host alone, with the host-pointer rules, and gives the same octets. */
+int hpk_write_frames(hpk_ctx* ctx, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                     const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap,
+                     uint32_t* wire_off, uint8_t* status, int flags);
+int hpk_write_frames_cpu(const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                         const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap,
+                         uint32_t* wire_off, uint8_t* status);
+
+/* Where hpk_h2_write_headers (below) frames its blocks. HPK_FRAME_WRITE_HOST (the default, and always without a
+ * context): hpk_write_frames_cpu's code. HPK_FRAME_WRITE_DEVICE (opt-in): hpk_write_frames with host pointers. */
+#define HPK_FRAME_WRITE_HOST 0    /* the default: the host framing */
+#define HPK_FRAME_WRITE_DEVICE 1
+int hpk_ctx_set_frame_write(hpk_ctx* ctx, int kind);
+/* Testing only: hpk_h2_write_headers calls on this context that the device framing answered. */
+uint64_t hpk_test_frame_write_calls(const hpk_ctx* ctx);
+
 /* ---- HPACK header blocks: encode (the response path) ----------------------
  * hpk_henc mirrors hpack::Encoder (crates/loona-hpack/src/encoder.rs:172-335): one per
  * connection, holding the dynamic table, with the reference's single strategy (a header found
@@ -778,6 +826,22 @@ void hpk_henc_out_free(hpk_henc_out* out);
  * device frame scan of hpk_h2_read_frames (HPK_FRAME_SCAN_DEVICE) counts as one such batch: it fails
  * the same way before it touches the device, and every connection stays as it was. */
 void hpk_test_fail_batches(int n);
+
+/* The block encoder and the framing in one call: what a server writes for many responses' headers
+ * (send_data_maybe's header loop, crates/loona/src/h2/server.rs:470-508, behind Encoder::encode). max_frame is
+ * validated before anything else (an entry of 0 or above 0xFFFFFF: HPK_E_INVAL, the encoders untouched);
+ * hpk_henc_encode_blocks runs as the context selects it; block b's bytes are then framed for stream_id[b] (bit 31 =
+ * END_STREAM) and max_frame[b] as hpk_write_frames frames them. out->bytes are the wire octets and out->block_off
+ * (nblocks + 1 entries) is wire_off. The framing is on the host by default and without a context;
+ * hpk_ctx_set_frame_write(ctx, HPK_FRAME_WRITE_DEVICE) selects hpk_write_frames with host pointers for that step.
+ * By then the encoders' tables are committed, so a failure of the device framing, real or injected, is answered by
+ * the host framing and the call succeeds: hpk_test_fail_batches counts the device framing as one batch (use raw
+ * encoders, so that no Huffman batch takes the count first), and hpk_test_frame_write_calls tells which path
+ * answered. A wire total past HPK_MAX_OFFSET is HPK_E_INVAL with the encoders advanced (4 GiB of headers in one
+ * call). Free the result with hpk_henc_out_free. */
+int hpk_h2_write_headers(hpk_ctx* ctx, hpk_henc* const* encs, const uint8_t* fields, const uint32_t* field_off,
+                         const uint32_t* hdr_off, uint32_t nblocks, const uint32_t* stream_id, const uint32_t* max_frame,
+                         hpk_henc_out* out);
 
 /* ---- HPACK header blocks: the encoder's table half on the device ---------------------------
  * hpk_plan_blocks is the batch form of Encoder::encode (crates/loona-hpack/src/encoder.rs:210-264) without the
@@ -942,6 +1006,10 @@ int hpk_test_blkscan_geometry(uint32_t* wg_blocks);
 /* Testing only: the frame scan's geometry (hpk_scan_frames): the connections a workgroup of either pass walks,
  * one per lane. The tests place their connection counts relative to it. */
 int hpk_test_frmscan_geometry(uint32_t* wg_conns);
+
+/* Testing only: the frame write's geometry: the bytes of a destination tile and the blocks a workgroup's LDS window
+ * holds (more blocks of no octets than that in a row force a restage inside one tile). */
+int hpk_test_frmwrite_geometry(uint32_t* tile_bytes, uint32_t* lds_blocks);
 
 /* Library/kernel identification (for logs and the bench JSON). */
 const char* hpk_version(void);

@@ -45,6 +45,10 @@ HPK_BLOCK_SCAN_DEVICE = 1
 HPK_FRAME_SCAN_HOST = 0
 HPK_FRAME_SCAN_DEVICE = 1
 
+# hpk_ctx_set_frame_write (hpk.h)
+HPK_FRAME_WRITE_HOST = 0
+HPK_FRAME_WRITE_DEVICE = 1
+
 # hpk_ctx_set_block_apply (hpk.h)
 HPK_BLOCK_APPLY_HOST = 0
 HPK_BLOCK_APPLY_DEVICE = 1
@@ -128,6 +132,11 @@ EXPORTS = (
     "hpk_scan_frames",
     "hpk_frame_blocks",
     "hpk_ctx_set_frame_scan",
+    "hpk_write_frames",
+    "hpk_write_frames_cpu",
+    "hpk_ctx_set_frame_write",
+    "hpk_test_frame_write_calls",
+    "hpk_h2_write_headers",
     "hpk_henc_create",
     "hpk_henc_destroy",
     "hpk_henc_set_max_table_size",
@@ -148,6 +157,7 @@ EXPORTS = (
     "hpk_test_small_set_request",
     "hpk_test_blkscan_geometry",
     "hpk_test_frmscan_geometry",
+    "hpk_test_frmwrite_geometry",
     "hpk_ctx_set_decode_kernel",
     "hpk_ctx_set_small_mode",
     "hpk_version",
@@ -272,6 +282,23 @@ def lib() -> ctypes.CDLL:
             L.hpk_ctx_set_frame_scan.restype = ctypes.c_int
             L.hpk_test_frmscan_geometry.argtypes = [c_u32p]
             L.hpk_test_frmscan_geometry.restype = ctypes.c_int
+        if hasattr(L, "hpk_write_frames"):  # (likewise: no frame write)
+            L.hpk_write_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int]
+            L.hpk_write_frames.restype = ctypes.c_int
+            L.hpk_write_frames_cpu.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+            L.hpk_write_frames_cpu.restype = ctypes.c_int
+            L.hpk_ctx_set_frame_write.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.hpk_ctx_set_frame_write.restype = ctypes.c_int
+            L.hpk_test_frame_write_calls.argtypes = [ctypes.c_void_p]
+            L.hpk_test_frame_write_calls.restype = ctypes.c_uint64
+            L.hpk_test_frmwrite_geometry.argtypes = [c_u32p, c_u32p]
+            L.hpk_test_frmwrite_geometry.restype = ctypes.c_int
+            L.hpk_h2_write_headers.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HencOut)]
+            L.hpk_h2_write_headers.restype = ctypes.c_int
         if hasattr(L, "hpk_apply_blocks"):  # (likewise: no block apply)
             L.hpk_apply_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,

@@ -847,6 +847,82 @@ class HuffmanCodec:
             out_blob = out_blob[: int(block_off[nb].item()) & 0xFFFFFFFF]
         return out_blob, block_off
 
+    FRAME_WRITES = {"host": _lib.HPK_FRAME_WRITE_HOST, "device": _lib.HPK_FRAME_WRITE_DEVICE}
+
+    def set_frame_write(self, kind: str):
+        """'host' (the default) or 'device' (hpk_ctx_set_frame_write): where h2.write_headers frames the encoded
+        blocks with this codec. The same octets; 'device' runs write_frames' kernels on the staged blocks, and a
+        failure of that step is answered by the host framing."""
+        if kind not in self.FRAME_WRITES:
+            raise ValueError(f"frame write {kind!r} not in {tuple(self.FRAME_WRITES)}")
+        _lib.check(self._L.hpk_ctx_set_frame_write(self._h, self.FRAME_WRITES[kind]), "hpk_ctx_set_frame_write")
+
+    def _write_frames_call(self, blocks, block_off, stream_id, max_frame, out_blob, wire_off, status, device, sync):
+        dev = self.device if device else None
+        n = int(block_off.shape[0]) - 1
+        if n < 0:
+            raise ValueError("block_off needs nblocks+1 >= 1 entries")
+        pb, cap = _arg(blocks, "blocks", ("uint8",), 0, dev)
+        po, _ = _arg(block_off, "block_off", _OFF_DTYPES, n + 1, dev)
+        ps, _ = _arg(stream_id, "stream_id", _OFF_DTYPES, n, dev)
+        pm, _ = _arg(max_frame, "max_frame", _OFF_DTYPES, n, dev)
+        pout, out_cap = _arg(out_blob, "out_blob", ("uint8",), 0, dev)
+        pw, _ = _arg(wire_off, "wire_off", _OFF_DTYPES, n + 1, dev)
+        pst, _ = _arg(status, "status", ("uint8",), n, dev)
+        if device:
+            self._follow()
+            flags = _lib.HPK_PTR_DEVICE | (0 if sync else _lib.HPK_ASYNC)
+        else:
+            flags = _lib.HPK_PTR_HOST
+        rc = self._L.hpk_write_frames(self._h, pb, cap, po, ctypes.c_uint32(n), ps, pm, pout, out_cap, pw, pst, flags)
+        _lib.check(rc, "hpk_write_frames")
+
+    def write_frames(self, blocks, block_off, stream_id, max_frame, out_blob=None, wire_off=None, status=None, sync=False):
+        """hpk_write_frames: torch cuda tensors -> (out_blob, wire_off, status). Block b is
+        blocks[block_off[b] : block_off[b + 1]]; it goes out as one HEADERS frame and the CONTINUATION frames that
+        max_frame[b] (the peer's SETTINGS_MAX_FRAME_SIZE) demands, on stream stream_id[b] (bit 31: END_STREAM on the
+        HEADERS frame, scan_frames' convention), at out_blob[wire_off[b] : wire_off[b + 1]]. out_blob=None allocates
+        what always suffices when every frame size is at least 16 (blocks' size + 9 octets per 16 of it and per
+        block), cut to the total when sync=True; pass one for smaller frame sizes. Capacity rules as encode_packed:
+        the octets below the capacity are written, and with sync=True a total past it raises (HPK_E_NOSPACE)."""
+        import torch
+
+        n = int(block_off.shape[0]) - 1
+        dev = blocks.device
+        own = out_blob is None
+        if own:
+            size = int(blocks.numel())
+            out_blob = torch.empty(max(size + 9 * (size // 16 + max(n, 0) + 1), 1), dtype=torch.uint8, device=dev)
+        if wire_off is None:
+            wire_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[: max(n, 0)]
+        self._write_frames_call(blocks, block_off, stream_id, max_frame, out_blob, wire_off, status, True, sync)
+        if own and sync:
+            out_blob = out_blob[: int(wire_off[n].item()) & 0xFFFFFFFF]
+        return out_blob, wire_off, status
+
+    def write_frames_host(self, blocks, block_off, stream_id, max_frame, out_cap=None):
+        """hpk_write_frames with host pointers: numpy in -> (out_blob, wire_off, status), staged through the context
+        and synchronous. The offsets and the frame sizes are checked before anything is copied. out_cap defaults to
+        the wire total (computed here); with a smaller one the call raises (HPK_E_NOSPACE)."""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        block_off = np.ascontiguousarray(block_off, dtype=U32)
+        stream_id = np.ascontiguousarray(stream_id, dtype=U32)
+        max_frame = np.ascontiguousarray(max_frame, dtype=U32)
+        n = len(block_off) - 1
+        if out_cap is None:
+            lens = np.diff(block_off.astype(np.int64))
+            m = np.maximum(max_frame.astype(np.int64), 1)
+            out_cap = int((lens + 9 * np.maximum(-(-lens // m), 1)).sum()) if n > 0 else 0
+        out = np.zeros(max(int(out_cap), 1), dtype=np.uint8)[: int(out_cap)]
+        wire_off = np.zeros(n + 1, dtype=U32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)[: max(n, 0)]
+        if blocks.size == 0:
+            blocks = np.zeros(1, dtype=np.uint8)[:0]
+        self._write_frames_call(blocks, block_off, stream_id, max_frame, out, wire_off, status, False, True)
+        return out[: int(wire_off[n])], wire_off, status
+
     BLOCK_APPLIES = {"host": _lib.HPK_BLOCK_APPLY_HOST, "device": _lib.HPK_BLOCK_APPLY_DEVICE}
 
     def set_block_apply(self, kind: str):

@@ -1,6 +1,6 @@
 // hpk_calls_frames.hip — the HTTP/2 frame entry points of the C ABI (include/hpk.h): the frame scan, the gather of
-// its fragments into header blocks, and hpk_h2_read_frames' device path (hpk_h2.cpp reaches it through the pointer
-// that hpk_ctx_create installs).
+// its fragments into header blocks, the frame write, and the device paths of hpk_h2_read_frames and
+// hpk_h2_write_headers (hpk_h2.cpp reaches them through the pointers that hpk_ctx_create installs).
 #include <stdlib.h>
 
 #include "hpk_calls.h"
@@ -283,5 +283,88 @@ int hpk_frames_device(hpk_ctx* c, hpk_frmjob* job) {
     job->open_off = o.open_off;
     job->open_len = o.open_len;
     job->blk = o.blk;
+    return HPK_E_OK;
+}
+
+// The frame write's host form: offsets and frame sizes checked before anything is copied, the blocks staged in one
+// piece (at their own offsets) into the slot's scratch beside the arrays, the steps, wire_off and status read back
+// with exactly min(wire_off[n], out_cap) octets (the total is known here: the host sums the same lengths).
+static int frmwrite_host(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t n, const uint32_t* stream_id,
+                         const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap, uint32_t* wire_off, uint8_t* status) {
+    if (hpk_check_offsets(block_off, n, cap)) return HPK_E_INVAL;
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        if (!hpk_max_frame_ok(max_frame[b])) return hpk_set_err_msg("a max_frame of 0 or above 0xFFFFFF", HPK_E_INVAL);
+        total += hpk_wire_len(block_off[b + 1] - block_off[b], max_frame[b]);
+    }
+    if (n == 0) {
+        wire_off[0] = 0;
+        return HPK_E_OK;
+    }
+    // (a total past HPK_MAX_OFFSET: the device voids every block and no octet comes back)
+    const size_t get = total > HPK_MAX_OFFSET ? 0 : total < out_cap ? (size_t)total : out_cap;
+    const uint32_t lo = block_off[0], hi = block_off[n];
+    const hpk_lay_frmwrite l = hpk_layout_frmwrite(hi, n, get);
+    const size_t tmp = hpk_pack_tmp_bytes(n);
+    hpk_slot* s;
+    int rc;
+    if ((rc = hpk_slot_acquire(c, &s)) || (rc = hpk_slot_reserve(c, s, {{&s->fw_stage, l.bytes}, {&s->pk_tmp, tmp + 32}}))) return rc;
+    const hpk_stage g{c->stream, s->fw_stage.as<uint8_t>()};
+    HIP_TRY(g.up_range(l.in, blocks, lo, hi));
+    HIP_TRY(g.up(l.boff, block_off, (size_t)n + 1));
+    HIP_TRY(g.up(l.sid, stream_id, n));
+    HIP_TRY(g.up(l.mf, max_frame, n));
+    if ((rc = hpk_frmwrite_launch(c, g(l.in), hi, g(l.boff), n, g(l.sid), g(l.mf), g(l.out), (uint32_t)get, g(l.woff), g(l.st), s->pk_tmp.p)))
+        return rc;
+    HIP_TRY(g.back(wire_off, l.woff, (size_t)n + 1));
+    HIP_TRY(g.back(status, l.st, n));
+    HIP_TRY(g.back(out_blob, l.out, get));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = hpk_slot_commit(c, s)) || (rc = hpk_take_err(c))) return rc;
+    if (total > out_cap) return hpk_set_err_msg("the wire octets pass the output capacity", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The frame write (include/hpk.h).
+extern "C" int hpk_write_frames(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                                const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap,
+                                uint32_t* wire_off, uint8_t* status, int flags) {
+    if (!c || !block_off || !wire_off || (nblocks && (!stream_id || !max_frame || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (nblocks >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the frame write", HPK_E_INVAL);
+    if (cap > HPK_MAX_OFFSET) return hpk_set_err_msg("the frame write's blob passes HPK_MAX_OFFSET", HPK_E_INVAL);
+    if (nblocks && ((!blocks && cap) || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!(flags & HPK_PTR_DEVICE)) return frmwrite_host(c, blocks, cap, block_off, nblocks, stream_id, max_frame, out_blob, out_cap, wire_off, status);
+    if (nblocks == 0) return hpk_packed_empty(c, wire_off, out_cap, flags);
+    const size_t tmp = hpk_pack_tmp_bytes(nblocks);
+    hpk_slot* s;
+    int rc;
+    if ((rc = hpk_slot_acquire(c, &s)) || (rc = hpk_slot_reserve(c, s, {{&s->pk_tmp, tmp + 32}}))) return rc;
+    hpk_in_or_codes(c, &blocks, &cap);
+    hpk_out_or_tmp(s, tmp, &out_blob, &out_cap);
+    if ((rc = hpk_frmwrite_launch(c, blocks, (uint32_t)cap, block_off, nblocks, stream_id, max_frame, out_blob, hpk_clamp_cap(out_cap), wire_off,
+                                  status, s->pk_tmp.p)))
+        return rc;
+    if ((rc = hpk_slot_commit(c, s))) return rc;
+    return hpk_packed_end(c, wire_off + nblocks, out_cap, flags);
+}
+
+extern "C" int hpk_ctx_set_frame_write(hpk_ctx* c, int kind) {
+    if (!c || (kind != HPK_FRAME_WRITE_HOST && kind != HPK_FRAME_WRITE_DEVICE)) return hpk_set_err_msg("bad frame write", HPK_E_INVAL);
+    c->frame_write = kind;
+    return HPK_E_OK;
+}
+
+extern "C" uint64_t hpk_test_frame_write_calls(const hpk_ctx* c) { return c ? c->frame_write_calls : 0u; }
+
+// hpk_h2_write_headers' device framing (hpk_internal.h; HPK_FRAME_WRITE_DEVICE): hpk_write_frames with host pointers.
+int hpk_write_device(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                     const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap, uint32_t* wire_off,
+                     uint8_t* status) {
+    if (!c || c->frame_write != HPK_FRAME_WRITE_DEVICE) return HPK_FRAMES_NOT_SELECTED;
+    if (int rc = hpk_test_take_failure()) return rc;
+    if (int rc = hpk_write_frames(c, blocks, cap, block_off, nblocks, stream_id, max_frame, out_blob, out_cap, wire_off, status, HPK_PTR_HOST))
+        return rc;
+    c->frame_write_calls += 1;
     return HPK_E_OK;
 }

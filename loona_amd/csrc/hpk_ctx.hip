@@ -6,7 +6,7 @@
 
 #include "hpk_calls.h"
 
-#define HPK_VERSION "hpk 0.47 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block); block apply v1 (one wave per decoder: lane-parallel look and stage, records resolved in order against a ring in LDS); frame scan v1 (count pass, length scans, emit pass: one lane per connection; fragments gathered by the ordered pack); block plan v1 (a default-and-hash pass, then one wave per encoder: headers resolved in order against a hashed ring in LDS, 64 entries a search step, matches confirmed on bytes)"
+#define HPK_VERSION "hpk 0.48 gfx950 decode v42 (every batch: wave fills, each wave with its own LDS window and image, lookups in a 13-bit two-symbol table, the lane loop in rounds of four nested body steps with long codes taken once a round, longest-first queue sorted under the previous image's LDS read-out, the next fill's loads issued ahead of the write-back's stores, slot end offsets by DPP, nontemporal window loads stopping at the chunk's last byte, nontemporal write-back; chunks by guided self-scheduling from 4M literals, fixed 96-literal chunks below; fills and long-literal phase: body steps with no fit tests while >= 31 bits are left (29 with the 12-bit table), then the wave fills' tails as four masked lookups with no fit test per code (checked steps only for a 14..30-bit code or a cut code in the tail), a lane's first literal's tail from the word saved where its body ended and its status carried from that tail, and the other kernels' checked tails (the long phase's at its refill points); long literals one lane each streaming from HBM after the fills, dense ranges listed longest-first; literals of >= 8 KiB by a whole workgroup in speculative pieces; compacted-output form: wave fills packed per workgroup from an LDS cursor into a bound layout made from the input offsets, each lane storing its two literals in unaligned 16-byte pieces; small-call mode: a persistent kernel behind a host-mapped doorbell); encode v5 (byte-balanced workgroup ranges, start map and DPP segmented scan, run accumulator, LDS image, live chunks only; packed form: length pass, length scan, the same kernel into exact positions; string literals v1: length pass + form step, length scan, a tile kernel that writes prefix, H bit and the Huffman or raw payload); string-literal decode v1 (parse kernel, Huffman payloads gathered by the ordered pack, the packed form's region decode, merge, length scan, ordered pack with a source per string); block scan v1 (count pass, length scans, emit pass: one lane per block); block apply v1 (one wave per decoder: lane-parallel look and stage, records resolved in order against a ring in LDS); frame scan v1 (count pass, length scans, emit pass: one lane per connection; fragments gathered by the ordered pack); block plan v1 (a default-and-hash pass, then one wave per encoder: headers resolved in order against a hashed ring in LDS, 64 entries a search step, matches confirmed on bytes); frame write v1 (length scan, status pass, a tile kernel that makes each 16-byte chunk of the wire: frame headers in registers, payloads by the pack's aligned loads)"
 
 static thread_local std::string t_last_error;
 
@@ -75,6 +75,7 @@ extern "C" hpk_ctx* hpk_ctx_create(int device) {
     *c->h_err = 0;
     if ((e = hipHostGetDevicePointer((void**)&c->d_err, c->h_err, 0)) != hipSuccess) return fail("err flag pointer", e);
     hpk_h2_set_frames_device(&hpk_frames_device);  // hpk_h2_read_frames' way to the device frame scan (hpk_internal.h)
+    hpk_h2_set_write_device(&hpk_write_device);    // hpk_h2_write_headers' way to the device frame write
     return c;
 }
 

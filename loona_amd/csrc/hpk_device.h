@@ -76,12 +76,14 @@ struct hpk_slot {
     // form and of hpk_h2_read_frames' device path; and that path's lists and gathered blocks, sized once the totals
     // are known (hpk_frame_blocks keeps its nfrags + 1 packed offsets there)
     DevBuf fs_meta, fs_stage, fs_out;
+    // the frame write's host form (hpk_write_frames): the staged blocks, arrays and wire octets
+    DevBuf fw_stage;
     // every buffer above: the one list of them (hpk_ctx_destroy frees through it)
-    static constexpr size_t kBufs = 20;
+    static constexpr size_t kBufs = 21;
     template <class F>
     void each_buf(F f) {
         for (DevBuf* b : {&long_list, &cp_bound, &cp_tmp, &cp_cursor, &pk_scratch, &pk_bound, &pk_tmp, &str_stage, &sd_meta, &sd_hblob,
-                          &sd_stage, &bs_meta, &bs_stage, &bs_out, &ba_buf, &bp_hash, &bp_buf, &fs_meta, &fs_stage, &fs_out})
+                          &sd_stage, &bs_meta, &bs_stage, &bs_out, &ba_buf, &bp_hash, &bp_buf, &fs_meta, &fs_stage, &fs_out, &fw_stage})
             f(*b);
     }
 };
@@ -96,6 +98,8 @@ struct hpk_ctx {
     int block_apply = HPK_BLOCK_APPLY_HOST;  // hpk_ctx_set_block_apply
     int block_plan = HPK_BLOCK_PLAN_HOST;  // hpk_ctx_set_block_plan
     int frame_scan = HPK_FRAME_SCAN_HOST;  // hpk_ctx_set_frame_scan
+    int frame_write = HPK_FRAME_WRITE_HOST;  // hpk_ctx_set_frame_write
+    uint64_t frame_write_calls = 0;  // hpk_h2_write_headers calls the device framing answered (hpk_test_frame_write_calls)
     uint64_t plan_calls = 0;  // hpk_henc_encode_blocks calls the device-plan path answered (hpk_test_plan_calls)
     hpk_header* d_static = nullptr;  // hpk_static_table's 61 records, uploaded by the first hpk_apply_blocks
     hipStream_t own = nullptr;
@@ -287,5 +291,13 @@ int hpk_launch_frmemit(hpk_ctx* c, const uint8_t* blob, uint32_t cap, const uint
                        uint32_t* open_len, uint32_t opens_cap);
 int hpk_launch_frmboff(hpk_ctx* c, const uint32_t* dst_off, uint32_t nfrags, const hpk_fblock* blocks, uint32_t nblocks,
                        uint32_t* block_off);
+
+// The frame write's steps (hpk_frmwrite.hip), on the ctx stream: wire_off (nblocks + 1 entries) = the exclusive sum of
+// the blocks' wire lengths, a void block counting 0 (sticky flag), all 0 when the total passes HPK_MAX_OFFSET; status
+// HPK_OK or HPK_BAD_OFFSETS; then block b's frames to out_blob[wire_off[b] ..), of which only the octets below out_cap
+// are written. tmp: hpk_pack_tmp_bytes(nblocks) bytes of device scratch.
+int hpk_frmwrite_launch(hpk_ctx* c, const uint8_t* blocks, uint32_t cap, const uint32_t* block_off, uint32_t nblocks,
+                        const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, uint32_t out_cap,
+                        uint32_t* wire_off, uint8_t* status, void* tmp);
 
 __device__ __forceinline__ uint32_t hpk_bswap32(uint32_t x) { return __builtin_bswap32(x); }

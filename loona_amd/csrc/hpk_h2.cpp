@@ -23,6 +23,8 @@
 #include "../../include/hpk.h"
 #include "hpk_internal.h"
 
+int hpk_set_err_msg(const char* what, int code);  // hpk_ctx.hip: hpk_last_error's message
+
 namespace {
 
 enum : uint8_t { kData = 0x0, kHeaders = 0x1, kContinuation = 0x9 };
@@ -314,4 +316,123 @@ extern "C" void hpk_h2_out_free(hpk_h2_out* out) {
     free(out->conn_error);
     free(out->conn_consumed);
     memset(out, 0, sizeof *out);
+}
+
+// ---- the write side: header blocks to HEADERS and CONTINUATION frames --------------------------------------------
+// The reference queues a response's header block in send_data_maybe (crates/loona/src/h2/server.rs:470-508): while
+// the piece left is strictly longer than the peer's max frame size, a frame of that many octets without flags
+// (HEADERS first, CONTINUATION after), then the last piece with END_HEADERS; Frame::write_into
+// (crates/loona-h2/src/lib.rs:413-422) puts the 9-octet header in front of each.
+namespace {
+
+// one frame header to p
+void put_frame_header(uint8_t* p, uint32_t len, uint8_t type, uint8_t flags, uint32_t sid) {
+    p[0] = (uint8_t)(len >> 16), p[1] = (uint8_t)(len >> 8), p[2] = (uint8_t)len;
+    p[3] = type, p[4] = flags;
+    sid &= 0x7FFFFFFFu;
+    p[5] = (uint8_t)(sid >> 24), p[6] = (uint8_t)(sid >> 16), p[7] = (uint8_t)(sid >> 8), p[8] = (uint8_t)sid;
+}
+
+// n octets from src to the wire position `at` of out, clipped at lim
+void put_clipped(uint8_t* out, uint64_t at, uint64_t lim, const uint8_t* src, size_t n) {
+    if (at >= lim || n == 0) return;
+    memcpy(out + at, src, (size_t)(lim - at < n ? lim - at : n));
+}
+
+}  // namespace
+
+extern "C" int hpk_write_frames_cpu(const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                                    const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap,
+                                    uint32_t* wire_off, uint8_t* status) {
+    if (!block_off || !wire_off || (nblocks && (!stream_id || !max_frame || !status))) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    if (nblocks >= 0x7FFFFFFFu) return hpk_set_err_msg("too many blocks for the frame write", HPK_E_INVAL);
+    if (cap > HPK_MAX_OFFSET) return hpk_set_err_msg("the frame write's blob passes HPK_MAX_OFFSET", HPK_E_INVAL);
+    if (nblocks && ((!blocks && cap) || (!out_blob && out_cap))) return hpk_set_err_msg("null blob", HPK_E_INVAL);
+    // the host-pointer rules: everything checked before anything is written
+    for (uint32_t b = 0; b < nblocks; ++b)
+        if (block_off[b + 1] < block_off[b]) return hpk_set_err_msg("offsets must be non-decreasing", HPK_E_INVAL);
+    if (block_off[nblocks] > cap) return hpk_set_err_msg("offsets pass the blob's capacity", HPK_E_INVAL);
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        if (!hpk_max_frame_ok(max_frame[b])) return hpk_set_err_msg("a max_frame of 0 or above 0xFFFFFF", HPK_E_INVAL);
+        total += hpk_wire_len(block_off[b + 1] - block_off[b], max_frame[b]);
+    }
+    if (total > HPK_MAX_OFFSET) {  // every block void, as the device has it
+        for (uint32_t b = 0; b <= nblocks; ++b) wire_off[b] = 0;
+        for (uint32_t b = 0; b < nblocks; ++b) status[b] = HPK_BAD_OFFSETS;
+        return hpk_set_err_msg("the wire octets pass HPK_MAX_OFFSET", HPK_E_INVAL);
+    }
+    const uint64_t lim = total < out_cap ? total : out_cap;
+    uint64_t at = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        wire_off[b] = (uint32_t)at;
+        status[b] = HPK_OK;
+        const uint8_t* p = blocks + block_off[b];
+        size_t left = block_off[b + 1] - block_off[b];
+        const uint32_t M = max_frame[b], sid = stream_id[b];
+        bool first = true;
+        for (;;) {  // server.rs:470-508
+            const bool last = left <= M;
+            const size_t n = last ? left : M;
+            uint8_t h[9];
+            put_frame_header(h, (uint32_t)n, first ? kHeaders : kContinuation, (uint8_t)((last ? kEndHeaders : 0) | (first && (sid >> 31) ? kEndStream : 0)), sid);
+            put_clipped(out_blob, at, lim, h, 9);
+            put_clipped(out_blob, at + 9, lim, p, n);
+            at += 9 + n;
+            p += n;
+            left -= n;
+            first = false;
+            if (last) break;
+        }
+    }
+    wire_off[nblocks] = (uint32_t)at;
+    if (total > out_cap) return hpk_set_err_msg("the wire octets pass the output capacity", HPK_E_NOSPACE);
+    return HPK_E_OK;
+}
+
+// The device half's frame write (hpk_internal.h: hpk_write_device), installed by hpk_ctx_create; null where only the
+// host half is linked.
+static std::atomic<hpk_write_device_fn> g_write_device{nullptr};
+void hpk_h2_set_write_device(hpk_write_device_fn fn) { g_write_device.store(fn, std::memory_order_relaxed); }
+
+extern "C" int hpk_h2_write_headers(hpk_ctx* ctx, hpk_henc* const* encs, const uint8_t* fields, const uint32_t* field_off,
+                                    const uint32_t* hdr_off, uint32_t nblocks, const uint32_t* stream_id, const uint32_t* max_frame,
+                                    hpk_henc_out* out) {
+    if (!out) return HPK_E_INVAL;
+    memset(out, 0, sizeof *out);
+    if (nblocks && (!stream_id || !max_frame)) return hpk_set_err_msg("null argument", HPK_E_INVAL);
+    for (uint32_t b = 0; b < nblocks; ++b)  // before anything else: the encoders stay as they are
+        if (!hpk_max_frame_ok(max_frame[b])) return hpk_set_err_msg("a max_frame of 0 or above 0xFFFFFF", HPK_E_INVAL);
+    hpk_henc_out blk;
+    if (const int rc = hpk_henc_encode_blocks(ctx, encs, fields, field_off, hdr_off, nblocks, &blk)) return rc;
+    // from here on the encoders' tables are committed
+    static const uint32_t no_blocks[1] = {0};
+    const uint32_t* boff = blk.block_off ? blk.block_off : no_blocks;
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) total += hpk_wire_len(boff[b + 1] - boff[b], max_frame[b]);
+    int rc = HPK_E_OK;
+    std::vector<uint8_t> status(nblocks ? nblocks : 1);
+    if (total > HPK_MAX_OFFSET) rc = hpk_set_err_msg("the wire octets pass HPK_MAX_OFFSET", HPK_E_INVAL);
+    if (!rc) {
+        out->bytes = (uint8_t*)malloc(total ? (size_t)total : 1);
+        out->block_off = (uint32_t*)malloc(((size_t)nblocks + 1) * sizeof(uint32_t));
+        if (!out->bytes || !out->block_off) rc = hpk_set_err_msg("out of memory", HPK_E_INVAL);
+    }
+    if (!rc) {
+        int on_device = HPK_FRAMES_NOT_SELECTED;
+        if (const hpk_write_device_fn fn = ctx ? g_write_device.load(std::memory_order_relaxed) : nullptr)
+            on_device = fn(ctx, blk.bytes, blk.len, boff, nblocks, stream_id, max_frame, out->bytes, (size_t)total, out->block_off,
+                           status.data());
+        if (on_device != HPK_E_OK)  // not selected, or it failed: the host framing answers
+            rc = hpk_write_frames_cpu(blk.bytes, blk.len, boff, nblocks, stream_id, max_frame, out->bytes, (size_t)total,
+                                      out->block_off, status.data());
+    }
+    hpk_henc_out_free(&blk);
+    if (rc) {
+        hpk_henc_out_free(out);
+        return rc;
+    }
+    out->len = (size_t)total;
+    out->n_blocks = nblocks;
+    return HPK_E_OK;
 }

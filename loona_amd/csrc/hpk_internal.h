@@ -123,5 +123,28 @@ enum { HPK_FRAMES_NOT_SELECTED = 1 };
 typedef int (*hpk_frames_device_fn)(hpk_ctx* c, hpk_frmjob* job);
 void hpk_h2_set_frames_device(hpk_frames_device_fn fn);  // hpk_h2.cpp
 int hpk_frames_device(hpk_ctx* c, hpk_frmjob* job);      // hpk_calls_frames.hip
+// The frame write's host arithmetic (hpk_h2.cpp, hpk_calls_frames.hip): a header block of L octets takes
+// max(1, ceil(L / m)) frames of 9 octets more each for a frame size of m >= 1. The device states the same in
+// hpk_frmwrite.h (fw_frames, fw_wire_len: __device__ code the host units cannot include);
+// tests/test_frmwrite_emulation.py and tests/test_frames_write_cases.py hold both to the one Python model.
+static inline uint64_t hpk_wire_len(uint32_t L, uint32_t m) {
+    const uint64_t f = (uint64_t)(L / m) + (L % m != 0u ? 1u : 0u);
+    return (uint64_t)L + 9u * (f ? f : 1u);
+}
+static inline bool hpk_max_frame_ok(uint32_t m) { return m >= 1u && m <= 0xFFFFFFu; }
+
+// hpk_h2_write_headers' device framing (hpk_calls_frames.hip: hpk_write_device; used by hpk_h2.cpp,
+// HPK_FRAME_WRITE_DEVICE), reached like the frame scan above through a pointer that hpk_h2.cpp defines and
+// hpk_ctx_create installs (hpk_h2_set_write_device). The installed function takes hpk_write_frames' host-pointer
+// arguments. It returns HPK_FRAMES_NOT_SELECTED for a context on HPK_FRAME_WRITE_HOST, and else HPK_E_OK with the
+// octets and wire_off on the host (the context's count of answered calls raised), or a negative code: the caller
+// then frames on the host.
+typedef int (*hpk_write_device_fn)(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                                   const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap,
+                                   uint32_t* wire_off, uint8_t* status);
+void hpk_h2_set_write_device(hpk_write_device_fn fn);  // hpk_h2.cpp
+int hpk_write_device(hpk_ctx* c, const uint8_t* blocks, size_t cap, const uint32_t* block_off, uint32_t nblocks,
+                     const uint32_t* stream_id, const uint32_t* max_frame, uint8_t* out_blob, size_t out_cap, uint32_t* wire_off,
+                     uint8_t* status);  // hpk_calls_frames.hip
 // hpk_henc.cpp: hpk_test_fail_batches' count, taken by one: 0, or the injected failure's code with its message set
 int hpk_test_take_failure();

@@ -307,3 +307,23 @@ static inline hpk_lay_frmout hpk_layout_frmout(size_t nb, size_t nf, size_t no, 
     l.bytes = k.end + out_cap + 16;
     return l;
 }
+
+// fw_stage, the frame write's host form: blocks | block_off | stream_id | max_frame | wire_off | status | out
+struct hpk_lay_frmwrite {
+    hpk_at<uint8_t> in, st, out;
+    hpk_at<uint32_t> boff, sid, mf, woff;
+    size_t bytes;
+};
+static inline hpk_lay_frmwrite hpk_layout_frmwrite(size_t hi, size_t nblocks, size_t dcap) {
+    hpk_carve k;
+    hpk_lay_frmwrite l;
+    l.in = k.blob(hi);
+    l.boff = k.take<uint32_t>(nblocks + 1);
+    l.sid = k.take<uint32_t>(nblocks);
+    l.mf = k.take<uint32_t>(nblocks);
+    l.woff = k.take<uint32_t>(nblocks + 1);
+    l.st = k.take<uint8_t>(nblocks);
+    l.out = {k.end};
+    l.bytes = k.end + dcap + 16;
+    return l;
+}

@@ -153,3 +153,68 @@ def frame(ftype: int, flags: int, stream_id: int, payload: bytes) -> bytes:
     n = len(payload)
     return bytes([n >> 16 & 255, n >> 8 & 255, n & 255, ftype, flags]) + (stream_id & 0x7FFFFFFF).to_bytes(4, "big") + \
         bytes(payload)
+
+
+def write_frames_cpu(blocks, block_off, stream_ids, max_frame_sizes, out_cap=None):
+    """hpk_write_frames_cpu: numpy in -> (wire octets, wire_off, status, return code). Block b =
+    blocks[block_off[b] : block_off[b+1]] becomes one HEADERS frame and the CONTINUATION frames that
+    max_frame_sizes[b] demands (server.rs:470-508), stream_ids[b]'s bit 31 asking for END_STREAM. out_cap defaults
+    to what the blocks need. The code is returned, not raised: HPK_E_NOSPACE (-2) still fills the arrays."""
+    L = _lib.lib()
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+    block_off = np.ascontiguousarray(block_off, dtype=np.uint32)
+    sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+    mf = np.ascontiguousarray(max_frame_sizes, dtype=np.uint32)
+    n = len(block_off) - 1
+    if len(sid) != n or len(mf) != n:
+        raise ValueError("one stream id and one frame size per block")
+    if out_cap is None:
+        lens = np.diff(block_off.astype(np.int64))
+        m = np.maximum(mf.astype(np.int64), 1)
+        out_cap = int((np.maximum(lens, 0) + 9 * np.maximum(-(-lens // m), 1)).sum()) if n > 0 else 0
+    out = np.full(max(int(out_cap), 1), 0xA5, dtype=np.uint8)
+    wire_off = np.zeros(n + 1, dtype=np.uint32)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    data = blocks if blocks.size else np.zeros(1, dtype=np.uint8)
+    rc = L.hpk_write_frames_cpu(data.ctypes.data, blocks.size, block_off.ctypes.data, n, sid.ctypes.data if n else None,
+                                mf.ctypes.data if n else None, out.ctypes.data, int(out_cap), wire_off.ctypes.data,
+                                status.ctypes.data if n else None)
+    return out[: int(out_cap)], wire_off, status[:n], rc
+
+
+def write_headers(encoders, header_lists, stream_ids, max_frame_sizes, codec=None):
+    """Many responses' headers -> the octets to send, one bytes object per block (hpk_h2_write_headers):
+    header_lists[b] = [(name, value)] is encoded with encoders[b] (hpack.Encoder; the blocks of one encoder in list
+    order, as hpack.encode_blocks) and framed for stream stream_ids[b] (bit 31: END_STREAM on the HEADERS frame) as
+    one HEADERS frame and the CONTINUATION frames max_frame_sizes[b], the peer's SETTINGS_MAX_FRAME_SIZE, demands
+    (server.rs:470-508). A frame size of 0 or above 0xFFFFFF raises before any encoder is touched. codec=None: all
+    on the host; with a codec the encode goes as it selects, and codec.set_frame_write('device') frames on the
+    device too."""
+    L = _lib.lib()
+    n = len(encoders)
+    if not (len(header_lists) == len(stream_ids) == len(max_frame_sizes) == n):
+        raise ValueError("one header list, stream id and frame size per encoder")
+    parts, off, hoff = [], [0], [0]
+    for headers in header_lists:
+        for name, value in headers:
+            for x in (name, value):
+                parts.append(bytes(x))
+                off.append(off[-1] + len(x))
+        hoff.append(hoff[-1] + len(headers))
+    if off[-1] >= 2**32:
+        raise ValueError("header fields of one call must stay below 4 GiB")
+    fields = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8).copy()
+    off32 = np.asarray(off, dtype=np.uint32)
+    hoff32 = np.asarray(hoff, dtype=np.uint32)
+    sid = np.asarray(list(stream_ids) or [0], dtype=np.uint32)
+    mf = np.asarray(list(max_frame_sizes) or [1], dtype=np.uint32)
+    encs = (ctypes.c_void_p * max(n, 1))(*[e._h for e in encoders])
+    out = _lib.HencOut()
+    ctx = codec._h if codec is not None else None
+    _lib.check(L.hpk_h2_write_headers(ctx, encs, fields.ctypes.data, off32.ctypes.data, hoff32.ctypes.data, n, sid.ctypes.data,
+                                      mf.ctypes.data, ctypes.byref(out)), "hpk_h2_write_headers")
+    try:
+        data = ctypes.string_at(out.bytes, out.len) if out.len else b""
+        return [data[out.block_off[b] : out.block_off[b + 1]] for b in range(n)]
+    finally:
+        L.hpk_henc_out_free(ctypes.byref(out))
